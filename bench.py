@@ -12,6 +12,18 @@ Input is resident in HBM before timing; the output (16-bit PCM, what the referen
 writes) stays in HBM.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5] [--strong]
+                    [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline figure needs: set-up, W warm-up steps, the graph
+capture and soak, the K timed steps, then one JSON line (value, ms_per_step, the step's
+configuration, the whole-step roofline fractions computed from ms_per_step).
+--dump-outputs DIR writes what the timed path returned in its last step as DIR/y.npy
+(float32; a fixed seeded sample of whole blocks when the output is longer than
+DUMP_MAX_FRAMES) and DIR/y_frames.npy (the frame index of every row of y).
+--full adds every measurement that takes runs of its own: the host-inclusive and
+double-buffered rates, per-stage HIP-event times and the dominant kernel's roofline,
+the CPU baseline and bit-for-bit parity against the C oracle, and at N = 1 the other
+configs, rates and inputs.
 
 --gpus N > 1 without a launcher starts the N ranks itself (a child
 `python -m torch.distributed.run --nproc-per-node N`, one process per GPU); under a
@@ -21,8 +33,8 @@ c2 = configs[1] (EQ + loudnorm + alimiter), c4 = configs[3] (8 whole 4-minute tr
 per GPU, track-sharded, no exchange), c5 = configs[4] (60 min at 96 kHz per GPU).
 --strong: ONE track of the config's length split over the N ranks (configs[4] as
 BASELINE.json states it: one 60-min 96 kHz track chunk-sharded over 8 GPUs).
-At N = 1 the default run also times C2, C4 and C5 on the GPU (``other_configs``:
-hipGraph replays, no CPU leg), so every config has a number from the driver's run.
+At N = 1 a --full run also times C2, C4 and C5 on the GPU (``other_configs``:
+hipGraph replays), so every config has a number from one run.
 """
 import argparse
 import json
@@ -395,6 +407,38 @@ def load_traffic(config):
         return None
 
 
+DUMP_MAX_FRAMES = 1 << 21      # rows per dumped array: 16 MB of float32 stereo + 16 MB of indices
+DUMP_BLOCK = 4096              # a longer output is sampled in whole blocks of this many frames
+DUMP_SEED = 20250101
+
+
+def dump_frames(n):
+    """the frames of an n-frame output that --dump-outputs keeps: all of them up to
+    DUMP_MAX_FRAMES, else the first and the last block and a seeded choice of the others
+    (the same for every run and every build)"""
+    if n <= DUMP_MAX_FRAMES:
+        return np.arange(n, dtype=np.int64)
+    nb = (n + DUMP_BLOCK - 1) // DUMP_BLOCK
+    rng = np.random.default_rng(DUMP_SEED)
+    pick = rng.choice(np.arange(1, nb - 1), DUMP_MAX_FRAMES // DUMP_BLOCK - 2, replace=False)
+    blocks = np.sort(np.concatenate([[0, nb - 1], pick])).astype(np.int64)
+    idx = (blocks[:, None] * DUMP_BLOCK + np.arange(DUMP_BLOCK, dtype=np.int64)[None, :]).reshape(-1)
+    return idx[idx < n]
+
+
+def dump_outputs(path, y, rank, world):
+    """--dump-outputs: the tensor the timed path returned in its last step (int16
+    [frames, C], in HBM) as float32 <path>/y.npy, with the frame index of every row in
+    <path>/y_frames.npy (float64); at N > 1 every rank writes its own y_rank<r> pair"""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    idx = dump_frames(int(y.shape[0]))
+    rows = y.index_select(0, torch.from_numpy(idx).to(y.device)).cpu().numpy()
+    tag = "" if world == 1 else "_rank%d" % rank
+    np.save(os.path.join(path, "y%s.npy" % tag), rows.astype(np.float32))
+    np.save(os.path.join(path, "y_frames%s.npy" % tag), idx.astype(np.float64))
+
+
 def launch_plan(gpus, env, argv=None, port=None):
     """How this invocation runs its --gpus N ranks (decided before any GPU call):
       ("run", None)       -- one process per rank already: WORLD_SIZE == --gpus (a launcher
@@ -447,13 +491,19 @@ def main():
     ap.add_argument("--seg-frames", type=int, default=128)
     ap.add_argument("--env-warm", type=int, default=None,
                     help="compressor envelope warm-up frames (default: the plan's, 2048)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's output to DIR/y.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beside the headline figure (host-inclusive "
+                         "rates, per-stage times and kernel roofline, CPU baseline and oracle parity, "
+                         "the other configs / rates / inputs); the --no-* options trim it")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-pipeline", action="store_true", help="skip the double-buffered host rate")
     ap.add_argument("--eager", action="store_true", help="launch every kernel from the host")
     ap.add_argument("--strong", action="store_true",
                     help="strong scaling: one track of the config's length split over the ranks")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the GPU-only timings of the other configs (N = 1 default run)")
+                    help="skip the timings of the other configs (N = 1 --full run)")
     ap.add_argument("--dist-backend", default="nccl",
                     help="nccl (= RCCL on ROCm); gloo only to rehearse N ranks on one GPU")
     ap.add_argument("--one-device", action="store_true",
@@ -487,7 +537,6 @@ def main():
     import numpy as np
     import torch
     import torch.distributed as dist
-    from amx import capi, synth
     from amx.dist import ShardedBatch, ShardedTrack
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -560,10 +609,13 @@ def main():
     flush = getattr(runner, "flush", None) if graph else None
     barrier()
     t0 = time.perf_counter()
+    y_last = None
     for _ in range(steps):
-        run()
+        y_last = run()
     if flush is not None:
-        flush()          # the pipelined N > 1 replay resolves its last step here
+        y_fin = flush()  # the pipelined N > 1 replay resolves its last step here
+        if y_fin is not None:
+            y_last = y_fin
     barrier()
     elapsed = time.perf_counter() - t0
     if use_dist:
@@ -575,6 +627,98 @@ def main():
     samples_rank = job.info.out_frames * 2
     value = samples_total * steps / elapsed / 1e6
 
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, y_last, rank, world)
+    report = job.fetch_report(raise_dynamic=False)
+    # whole-step fractions from the committed PMC summaries and ms_per_step (no runs of their own)
+    traffic = load_traffic(args.config)
+    step_traffic = None
+    if traffic:
+        step_traffic = int(sum(v["hbm_bytes"] * PER_STEP.get(k, 1) for k, v in traffic.items()
+                               if k.startswith(PIPELINE_PREFIX)))
+    flops = load_flops(args.config)
+    chain_flops = None
+    if flops:
+        f64 = sum(v["fp64_flops"] * PER_STEP.get(k, 1) for k, v in flops.items() if k.startswith(PIPELINE_PREFIX))
+        f32 = sum(v["fp32_flops"] * PER_STEP.get(k, 1) for k, v in flops.items() if k.startswith(PIPELINE_PREFIX))
+        chain_flops = {
+            "fp64_flops_per_step": int(f64), "fp32_flops_per_step": int(f32),
+            "fp64_per_sample": round(f64 / samples_rank, 1), "fp32_per_sample": round(f32 / samples_rank, 1),
+            "achieved_fp64": round(f64 / (ms_per_step / 1e3) / 1e12, 3),
+            "peak_fp64": FP64_PEAK_TFS, "unit": "TFLOP/s",
+            "frac": round(f64 / (ms_per_step / 1e3) / 1e12 / FP64_PEAK_TFS, 4),
+            "frac_fp64_plus_fp32": round((f64 / FP64_PEAK_TFS + f32 / FP32_PEAK_TFS) / (ms_per_step / 1e3) / 1e12, 4),
+            "source": "profiles/flops_%s.json (rocprofv3 SQ_INSTS_VALU_{FMA,ADD,MUL,TRANS}_{F64,F32} x 64 "
+                      "lanes, FMA x 2; issued lanes, per launch) over the measured step time" % args.config}
+
+    line = {
+        "metric": "mastered Msamples/sec (48 kHz stereo f32) at 1/2/4/8 GPUs; % HBM roofline",
+        "value": round(value, 3), "unit": "Msamples/s", "n_gpus": world, "steps": steps,
+        "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
+        "scaling": "strong" if args.strong else "weak", "vs_baseline": None, "dtype": "f64",
+        "data": "synthetic (%s, seeded per rank / track)" % synth_generator(
+            per_track if batch else runner.local_frames, fs),
+        "config": {"workload": (WORKLOAD_STRONG.get(args.config, WORKLOAD[args.config]) if args.strong
+                                else WORKLOAD[args.config]), "sample_rate": fs,
+                   "settings": args.config, "seconds_per_track": args.seconds,
+                   "tracks_per_gpu": len(runner.tracks) if batch else 1,
+                   "seg_frames": args.seg_frames,
+                   "parallelism": ("track-shard x%d" if batch else "chunk-shard x%d") % world,
+                   "exchanges": ("%s collectives" % dist.get_backend()) if use_dist and not batch else None,
+                   "launch": ("hipGraph replay" if (world == 1 and not args.force_exchange) or batch else
+                              ("one hipGraph per step, RCCL collectives captured, two slots pipelined"
+                               if args.dist_backend == "nccl" else
+                               "hipGraph segments + eager (host-staged) collectives")) if graph else "eager"},
+        "timed_region_s": round(elapsed, 4), "soak": {"seconds": round(soak_s, 3), "replays": n_soak},
+        "chain_roofline": {
+            "bytes_per_step": int(CHAIN_BYTES * samples_rank),
+            "achieved": round(CHAIN_BYTES * samples_rank / (ms_per_step / 1e3) / 1e9, 2),
+            "frac": round(CHAIN_BYTES * samples_rank / (ms_per_step / 1e3) / 1e9 / HBM_PEAK_GBS, 4),
+            "frac_end_to_end": round(E2E_BYTES * samples_rank / (ms_per_step / 1e3) / 1e9 / HBM_PEAK_GBS, 4),
+            "step_traffic": step_traffic,
+            "what": "whole step (every kernel) at SURVEY §8(d)'s 8 B/sample chain and 16 B/sample "
+                    "end-to-end; step_traffic = the PMC bytes of every pipeline kernel per step"},
+        "chain_flop_frac": chain_flops,
+        "plan": {"segments": int(job.info.n_segments), "seg_frames": int(job.info.seg_frames),
+                 "scan_window_eq": int(job.info.scan_levels_eq),
+                 "scan_window_xover": int(job.info.scan_levels_xover),
+                 "scan_window_kw": int(job.info.scan_levels_kw)},
+        "limiter_fast": report.get("limiter_fast"),
+        "loudnorm": report.get("stats"),
+        "loudnorm_mode": report.get("modes"),
+    }
+    if args.input == "dynamic":
+        # value counts the chain's input-rate samples; the step ends in the 192 kHz stream
+        line["dynamic"] = dict(getattr(runner, "dyn_info", None) or {}, input=args.input)
+        line["data"] += "; quiet programme with full-scale bursts (loudnorm dynamic mode)"
+    if args.full:
+        # every rank runs these steps (at N > 1 they hold collectives)
+        line.update(step_extras(args, runner, d_in, x, run, barrier, steps, fs, settings, per_track, batch,
+                                samples_total, samples_rank))
+    full_cpu = args.full and rank == 0 and world == 1
+    if full_cpu and not args.no_cpu_baseline and args.input == "mix":
+        line.update(cpu_leg(args, runner, x, fs, settings, job, batch))
+    if full_cpu and args.config == "c3" and not args.no_other_configs:
+        line["other_configs"] = other_configs(args)
+        line["other_rates"] = other_rates(args)
+        line["other_inputs"] = {"dynamic": other_inputs(args)}
+    if rank == 0:
+        print(json.dumps(line), flush=True)
+    # the captured graphs (RCCL nodes at N > 1) go before the process group
+    runner.close()
+    if use_dist:
+        dist.destroy_process_group()
+
+
+def step_extras(args, runner, d_in, x, run, barrier, steps, fs, settings, per_track, batch,
+                samples_total, samples_rank):
+    """--full: the measurements on the bench's own step that take runs of their own,
+    after the timed region: the host-inclusive rates, the per-stage HIP-event times, and
+    the dominant kernel's and k_front2's rooflines"""
+    import torch
+    from amx import capi, synth
+    job = runner.job
+    world = runner.world
     # host-inclusive rate (reported beside `value`, never as it): pinned H2D of the f32
     # input, the step, D2H of the int16 output, serialised on the stream
     host_incl = None
@@ -631,7 +775,6 @@ def main():
     per_stage = {k: v / n_ev for k, v in per_stage.items()}
     job.stage_events = None
     env_ctr = job.env_counters() if settings.get("multiband") else None
-    report = job.fetch_report(raise_dynamic=False)
     frames = runner.local_frames
     mb = bool(settings.get("multiband"))
     # dominant kernel: the slowest single-kernel stage
@@ -665,45 +808,8 @@ def main():
     model_bytes = stage_bytes(dom, frames, 2)
     traffic = load_traffic(args.config)
     dom_traffic = int(traffic[kern]["hbm_bytes"]) if traffic and kern in traffic else None
-    step_traffic = None
-    if traffic:
-        step_traffic = int(sum(v["hbm_bytes"] * PER_STEP.get(k, 1) for k, v in traffic.items()
-                               if k.startswith(PIPELINE_PREFIX)))
     f2_flops = front2_flops(frames, settings, mb)
-    flops = load_flops(args.config)
-    chain_flops = None
-    if flops:
-        f64 = sum(v["fp64_flops"] * PER_STEP.get(k, 1) for k, v in flops.items() if k.startswith(PIPELINE_PREFIX))
-        f32 = sum(v["fp32_flops"] * PER_STEP.get(k, 1) for k, v in flops.items() if k.startswith(PIPELINE_PREFIX))
-        chain_flops = {
-            "fp64_flops_per_step": int(f64), "fp32_flops_per_step": int(f32),
-            "fp64_per_sample": round(f64 / samples_rank, 1), "fp32_per_sample": round(f32 / samples_rank, 1),
-            "achieved_fp64": round(f64 / (ms_per_step / 1e3) / 1e12, 3),
-            "peak_fp64": FP64_PEAK_TFS, "unit": "TFLOP/s",
-            "frac": round(f64 / (ms_per_step / 1e3) / 1e12 / FP64_PEAK_TFS, 4),
-            "frac_fp64_plus_fp32": round((f64 / FP64_PEAK_TFS + f32 / FP32_PEAK_TFS) / (ms_per_step / 1e3) / 1e12, 4),
-            "source": "profiles/flops_%s.json (rocprofv3 SQ_INSTS_VALU_{FMA,ADD,MUL,TRANS}_{F64,F32} x 64 "
-                      "lanes, FMA x 2; issued lanes, per launch) over the measured step time" % args.config}
-
-    line = {
-        "metric": "mastered Msamples/sec (48 kHz stereo f32) at 1/2/4/8 GPUs; % HBM roofline",
-        "value": round(value, 3), "unit": "Msamples/s", "n_gpus": world, "steps": steps,
-        "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
-        "scaling": "strong" if args.strong else "weak", "vs_baseline": None, "dtype": "f64",
-        "data": "synthetic (%s, seeded per rank / track)" % synth_generator(
-            per_track if batch else runner.local_frames, fs),
-        "config": {"workload": (WORKLOAD_STRONG.get(args.config, WORKLOAD[args.config]) if args.strong
-                                else WORKLOAD[args.config]), "sample_rate": fs,
-                   "settings": args.config, "seconds_per_track": args.seconds,
-                   "tracks_per_gpu": len(runner.tracks) if batch else 1,
-                   "seg_frames": args.seg_frames,
-                   "parallelism": ("track-shard x%d" if batch else "chunk-shard x%d") % world,
-                   "exchanges": ("%s collectives" % dist.get_backend()) if use_dist and not batch else None,
-                   "launch": ("hipGraph replay" if (world == 1 and not args.force_exchange) or batch else
-                              ("one hipGraph per step, RCCL collectives captured, two slots pipelined"
-                               if args.dist_backend == "nccl" else
-                               "hipGraph segments + eager (host-staged) collectives")) if graph else "eager"},
-        "timed_region_s": round(elapsed, 4), "soak": {"seconds": round(soak_s, 3), "replays": n_soak},
+    return {
         "roofline": {"bound": "hbm", "kernel": kern, "stage": dom, "achieved": round(achieved, 2),
                      "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
                      "traffic": dom_traffic,
@@ -717,15 +823,6 @@ def main():
                                       "what": "the kernel's own minimum reads + writes (DESIGN.md §3.3)"},
                      "traffic_source": "profiles/traffic_%s.json (rocprofv3 FETCH_SIZE x2 + WRITE_SIZE, "
                                        "per launch)" % args.config},
-        "chain_roofline": {
-            "bytes_per_step": int(CHAIN_BYTES * samples_rank),
-            "achieved": round(CHAIN_BYTES * samples_rank / (ms_per_step / 1e3) / 1e9, 2),
-            "frac": round(CHAIN_BYTES * samples_rank / (ms_per_step / 1e3) / 1e9 / HBM_PEAK_GBS, 4),
-            "frac_end_to_end": round(E2E_BYTES * samples_rank / (ms_per_step / 1e3) / 1e9 / HBM_PEAK_GBS, 4),
-            "step_traffic": step_traffic,
-            "what": "whole step (every kernel) at SURVEY §8(d)'s 8 B/sample chain and 16 B/sample "
-                    "end-to-end; step_traffic = the PMC bytes of every pipeline kernel per step"},
-        "chain_flop_frac": chain_flops,
         "host_inclusive": host_incl,
         "roofline_fp64": {"bound": "fp64", "kernel": "k_front2",
                           "achieved": round(f2_flops / (per_stage["front2"] / 1e3) / 1e12, 2),
@@ -733,31 +830,8 @@ def main():
                           "frac": round(f2_flops / (per_stage["front2"] / 1e3) / 1e12 / FP64_PEAK_TFS, 4),
                           "flops_per_launch": int(f2_flops)},
         "stages_ms": {k: round(v, 4) for k, v in per_stage.items()},
-        "plan": {"segments": int(job.info.n_segments), "seg_frames": int(job.info.seg_frames),
-                 "scan_window_eq": int(job.info.scan_levels_eq),
-                 "scan_window_xover": int(job.info.scan_levels_xover),
-                 "scan_window_kw": int(job.info.scan_levels_kw)},
         "env_fixup": env_ctr,
-        "limiter_fast": report.get("limiter_fast"),
-        "loudnorm": report.get("stats"),
-        "loudnorm_mode": report.get("modes"),
     }
-    if args.input == "dynamic":
-        # value counts the chain's input-rate samples; the step ends in the 192 kHz stream
-        line["dynamic"] = dict(getattr(runner, "dyn_info", None) or {}, input=args.input)
-        line["data"] += "; quiet programme with full-scale bursts (loudnorm dynamic mode)"
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.input == "mix":
-        line.update(cpu_leg(args, runner, x, fs, settings, job, batch))
-    if rank == 0 and world == 1 and args.config == "c3" and not args.no_other_configs:
-        line["other_configs"] = other_configs(args)
-        line["other_rates"] = other_rates(args)
-        line["other_inputs"] = {"dynamic": other_inputs(args)}
-    if rank == 0:
-        print(json.dumps(line), flush=True)
-    # the captured graphs (RCCL nodes at N > 1) go before the process group
-    runner.close()
-    if use_dist:
-        dist.destroy_process_group()
 
 
 def cpu_leg(args, runner, x, fs, settings, job, batch):

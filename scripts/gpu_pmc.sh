@@ -3,15 +3,16 @@
 # FETCH_SIZE on gfx950 reports 1/2 of the bytes of wide coalesced reads
 # (MI355X_MICROARCH.md "HBM"): bench.py / DESIGN.md apply the x2 correction.
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
-mkdir -p gpurun_out
+OUT=${AMX_OUT:-out}
+mkdir -p "$OUT"
 export TMPDIR=/tmp
 TAG=${TAG:-r01}
-CMD="python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline ${BENCH_ARGS}"
+CMD="python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline ${BENCH_ARGS}"
 run() {
   local name=$1; shift
-  timeout -k 10 300 rocprofv3 --pmc "$@" -d gpurun_out/pmc_${TAG}_$name -o run --output-format csv -- $CMD > gpurun_out/pmc_${TAG}_$name.log 2>&1
+  timeout -k 10 300 rocprofv3 --pmc "$@" -d $OUT/pmc_${TAG}_$name -o run --output-format csv -- $CMD > $OUT/pmc_${TAG}_$name.log 2>&1
   local rc=$?
-  echo "rc=$rc" >> gpurun_out/pmc_${TAG}_$name.log
+  echo "rc=$rc" >> $OUT/pmc_${TAG}_$name.log
   return $rc
 }
 run sq SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_BUSY_CYCLES && \

@@ -41,6 +41,24 @@ def test_launcher_world_must_match():
     assert bench.launch_plan(0, {})[0] == "refuse"
 
 
+def test_dump_sample_is_fixed_and_bounded():
+    """--dump-outputs: every frame of a short output; of a long one the same whole blocks
+    on every call, first and last included, y.npy + y_frames.npy within 64 MB"""
+    import numpy as np
+    short = bench.dump_frames(1000)
+    assert short.tolist() == list(range(1000))
+    assert len(bench.dump_frames(bench.DUMP_MAX_FRAMES)) == bench.DUMP_MAX_FRAMES
+    for n in (bench.DUMP_MAX_FRAMES + 1, 14400000 - 37, 691200000):
+        idx = bench.dump_frames(n)
+        assert np.array_equal(idx, bench.dump_frames(n))
+        assert idx[0] == 0 and idx[-1] == n - 1
+        assert (np.diff(idx) > 0).all()
+        assert len(idx) <= bench.DUMP_MAX_FRAMES
+        assert len(idx) * (2 * 4 + 8) <= 64 * 1000 * 1000      # stereo float32 rows + float64 indices
+        starts = idx[::bench.DUMP_BLOCK]
+        assert (starts % bench.DUMP_BLOCK == 0).all()
+
+
 @pytest.mark.parametrize("env_world,gpus", [("2", 4), ("8", 1)])
 def test_mismatched_launch_exits_2_before_the_gpu(env_world, gpus):
     env = dict(os.environ, WORLD_SIZE=env_world, RANK="0", LOCAL_RANK="0")
