@@ -107,6 +107,7 @@ EXPORTS = ("amx_abi_version", "amx_last_error", "amx_build_id", "amx_plan_create
            "amx_loudnorm_192k", "amx_loudnorm_192k_ex", "amx_flac_info", "amx_flac_decode",
            "amx_plan_set_gate", "amx_loudnorm_192k_shard", "amx_loudnorm_192k_segments",
            "amx_loudnorm_192k_shard_window", "amx_publish_ctl", "amx_plan_set_limiter_trace",
+           "amx_plan_set_limiter_channels",
            "amx_mc_plan_create", "amx_mc_plan_free", "amx_mc_plan_get_info", "amx_mc_run_chunks",
            "amx_mc_split_pairs", "amx_mc_loudness_combine", "amx_mc_peak_pick", "amx_mc_limiter_out")
 PCM_FORMATS = {"u8": 0, "s16": 1, "s24": 2, "s32": 3, "f32": 4, "f64": 5,
@@ -143,6 +144,7 @@ def load(path=None):
     L.amx_env_counters.argtypes = [vp, vp, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32]
     L.amx_plan_set_gate.argtypes = [vp, vp]
     L.amx_plan_set_limiter_trace.argtypes = [vp, vp]
+    L.amx_plan_set_limiter_channels.argtypes = [vp, ctypes.c_int32]
     L.amx_mc_plan_create.argtypes = [ctypes.POINTER(ChainDesc), ctypes.POINTER(Chunk), ctypes.c_int32,
                                      ctypes.c_int32, ctypes.POINTER(vp)]
     L.amx_mc_plan_free.argtypes = [vp]

@@ -642,6 +642,9 @@ class MultiChannelJob:
         self.att = torch.ones(m, dtype=torch.float64, device=dev)
         capi.check(capi.load().amx_plan_set_limiter_trace(self.one.plan.h, capi.ptr(self.att)),
                    "amx_plan_set_limiter_trace")
+        # af_alimiter's attack slope is / (C B) * C: the peak signal's stereo run takes C there
+        capi.check(capi.load().amx_plan_set_limiter_channels(self.one.plan.h, C),
+                   "amx_plan_set_limiter_channels")
         self.report = {}
 
     _s = staticmethod(MasteringJob._s)

@@ -166,6 +166,7 @@ struct LimArgs {
     int halo_frames, fs, bs, seg_frames, warm_frames, max_segs, fast;
     int from_rest;          // amx_final_desc.from_rest: every span starts fresh, `state` is out only
     double *att;            // [out frames] each output frame's att (amx_plan_set_limiter_trace), or NULL
+    int slope_ch;           // channels of the stream the limiter stands for (amx_plan_set_limiter_channels)
     int64_t warm_cap;
     const double *gains;
     const int32_t *ctl;
@@ -184,6 +185,7 @@ struct Lim {
     int64_t n, tframe0;
     double g, level_in, level, level_out, limit, release;
     int fs, bs, halo, P0;
+    int sbs, sch;               // af_alimiter's buffer_size and channels in the attack slope: C B, C
     bool from_rest;             // the carried state is not read (LimArgs.from_rest)
     double *buffer, *nextdelta, *nextposd, *inb, *outb;   // LDS
     double att, delta;          // scalar state, identical in every lane between batches
@@ -282,6 +284,7 @@ __device__ int lim_seq(Lim &L, int nb, int pos, double s0v, double s1v, double d
                        double &o0, double &o1, double &oa, bool &nowidle) {
     const int lane = threadIdx.x & 63;
     const int bs = L.bs, channels = 2;
+    const int sbs = L.sbs, sch = L.sch;
     const double limit = L.limit;
     double att = L.att, delta = L.delta;
     int nextiter = L.nextiter, nextlen = L.nextlen;
@@ -301,7 +304,7 @@ __device__ int lim_seq(Lim &L, int nb, int pos, double s0v, double s1v, double d
             amx_wave_sync();
             double patt = fmin(limit / peak, 1.);
             double rdelta = (1.0 - patt) / (L.fs * L.release);
-            double d = (limit / peak - att) / bs * channels;
+            double d = (limit / peak - att) / sbs * sch;
             if (d < delta) {
                 delta = d;
                 if (lane == 0) {
@@ -552,6 +555,7 @@ __device__ void limiter_block(const LimArgs &a, int bx, int nbx, double *lim_lds
     L.level_in = a.level_in; L.level = a.level; L.level_out = a.level_out;
     L.limit = a.limit; L.release = a.release;
     L.fs = a.fs; L.bs = a.bs; L.halo = a.halo_frames;
+    L.sbs = a.bs / 2 * a.slope_ch; L.sch = a.slope_ch;
     L.from_rest = a.from_rest != 0;
     L.buffer = lim_lds; L.nextdelta = lim_lds + a.bs; L.nextposd = lim_lds + 2 * a.bs;
     L.inb = lim_lds + 3 * a.bs; L.outb = L.inb + 2 * AMX_LIM_BATCH;
@@ -783,6 +787,7 @@ hipError_t launch_final(const SpanDev *spans, int n_tracks, int64_t max_span, co
     fa.fast_cols = (ctl != nullptr || fast) ? (int)((max_span + per - 1) / per) : 0;
     fa.gate = ls.gate;
     a.att = ls.att;
+    a.slope_ch = ls.slope_channels;
     size_t lds = 0;
     if (general) {
         lds = limiter_lds_bytes(buffer_size);

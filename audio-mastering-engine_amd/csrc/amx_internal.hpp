@@ -390,6 +390,7 @@ struct LimScratch {
     int64_t warm_cap = 0;          // furthest warm-up start before a segment, frames
     const int32_t *gate = nullptr; // amx_plan_set_gate: k_final returns unless dynamic
     double *att = nullptr;         // amx_plan_set_limiter_trace: per output frame att, or NULL
+    int slope_channels = 2;        // amx_plan_set_limiter_channels: C of the attack slope / (C B) * C
 };
 size_t limiter_lds_bytes(int buffer_size);
 #define AMX_LIM_LDS_MAX (160 * 1024)   // gfx950: one workgroup may hold a CU's whole LDS

@@ -347,6 +347,7 @@ struct amx_plan {
     float *d_in_lut = nullptr;     // a stream chain's input table (amx_chain_desc.eq_in_lut), or NULL
     int sc = 0;                    // a stream chain (amx_chain_desc.stream_chain)
     double *lim_att = nullptr;     // amx_plan_set_limiter_trace
+    int32_t lim_channels = 2;      // amx_plan_set_limiter_channels
     float *d_lut_half = nullptr;   // the odd tanh table's half [0, 32768] (k_analog_h), or NULL
     unsigned int *d_pcnt = nullptr;   // k_peak_reduce's per-track block counter (self re-arming)
     int *d_ppart = nullptr;           // its per-block partial maxima
@@ -1803,6 +1804,13 @@ int amx_plan_set_limiter_trace(amx_plan *p, double *d_att) {
     return AMX_OK;
 }
 
+int amx_plan_set_limiter_channels(amx_plan *p, int32_t channels) {
+    if (!p) return fail(AMX_EINVAL, "null plan");
+    if (channels < 1 || channels > 8) return fail(AMX_EINVAL, "%d channels", channels);
+    p->lim_channels = channels < 2 ? 2 : channels;     // mono is limited as stereo (:190)
+    return AMX_OK;
+}
+
 int amx_plan_set_publish(amx_plan *p, int32_t *h_ctl) {
     if (!p) return fail(AMX_EINVAL, "null plan");
     p->publish = h_ctl;
@@ -2057,6 +2065,7 @@ int amx_finalize(amx_plan *p, const amx_final_desc *fd, const int16_t *d_x,
     }
     p->lim.gate = p->gate;
     p->lim.att = p->lim_att;
+    p->lim.slope_channels = p->lim_channels;
     HIPCHK(amx::launch_final(p->d_spans, p->n_tracks, p->max_span, d_x, d_halo, halo, d_gains, d_ctl,
                              fast ? 1 : 0, p->cd.fs, fd->level_in, level, fd->level_out, fd->limit,
                              fd->release_ms / 1000.0, bs, d_lim_state, sd, fd->from_rest, p->lim, d_y, st));
@@ -2250,6 +2259,7 @@ int amx_mc_run_chunks(amx_mc_plan *m, const void *d_in, int16_t *d_out, void *d_
 
 int amx_mc_split_pairs(const int16_t *d_y, int64_t frames, int32_t channels, int16_t *d_pairs, void *stream) {
     if (frames > 0 && (!d_y || !d_pairs)) return fail(AMX_EINVAL, "null argument");
+    if (channels < 1 || channels > 8) return fail(AMX_EINVAL, "%d channels", channels);
     HIPCHK(amx::launch_mc_split_pairs(d_y, frames, channels, d_pairs, (hipStream_t)stream));
     return AMX_OK;
 }
@@ -2257,6 +2267,7 @@ int amx_mc_split_pairs(const int16_t *d_y, int64_t frames, int32_t channels, int
 int amx_mc_loudness_combine(const double *d_hops, int64_t max_hops, const double *d_peak, int32_t channels,
                             double *d_hops1, double *d_peak1, void *stream) {
     if (!d_hops || !d_peak || !d_hops1 || !d_peak1 || max_hops <= 0) return fail(AMX_EINVAL, "null argument");
+    if (channels < 1 || channels > 8) return fail(AMX_EINVAL, "%d channels", channels);
     HIPCHK(amx::launch_mc_loudness_combine(d_hops, max_hops, d_peak, channels, d_hops1, d_peak1,
                                            (hipStream_t)stream));
     return AMX_OK;

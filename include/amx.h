@@ -482,6 +482,13 @@ AMX_API int amx_finalize(amx_plan *plan, const amx_final_desc *fd, const int16_t
  * doubles, or stops (NULL).  The idle path (AMX_CTL_FAST) writes nothing: att = 1. */
 AMX_API int amx_plan_set_limiter_trace(amx_plan *plan, double *d_att);
 
+/* (ABI 4, added without a layout change) The channel count C (1..8) of the stream the
+ * plan's limiter stands for: a stereo plan run over amx_mc_peak_pick's peak signal
+ * limits a C-channel file, and af_alimiter's attack slope is (limit / peak - att) /
+ * (C B) * C, which rounds differently from / (2 B) * 2 for C = 3, 5, 6, 7.  Only that
+ * expression takes C; the ring and every distance stay in stereo frames.  Default 2. */
+AMX_API int amx_plan_set_limiter_channels(amx_plan *plan, int32_t channels);
+
 /* ---------------------------------------------------------------------------------
  * (ABI 4) Files with more than two channels (3..8).  The reference keeps such a chunk
  * as ONE interleaved 1-D stream (:252): analog character, EQ and crossover run along

@@ -996,10 +996,10 @@ EXPORT int orc_ebur128_192k(const int16_t *x, int64_t n, int fs, int channels,
  * asc=0, level (auto level)=1, latency=0.  Input s16 -> double x/32768,
  * output double -> s16 llrint(x*32768) clipped.  Output is the input delayed
  * by buffer_size/channels - 1 frames (no latency compensation). */
-EXPORT void orc_alimiter(const int16_t *x, int64_t n, int fs, int channels,
-                         double level_in, double level_out, double limit,
-                         double attack_ms, double release_ms, int auto_level,
-                         int16_t *out) {
+static void alimiter_core(const int16_t *x, int64_t n, int fs, int channels,
+                          double level_in, double level_out, double limit,
+                          double attack_ms, double release_ms, int auto_level,
+                          int16_t *out, double *att_out) {
     double attack = attack_ms / 1000.0, release = release_ms / 1000.0;
     int buffer_size = (int)(fs * attack * channels);
     buffer_size -= buffer_size % channels;
@@ -1060,6 +1060,7 @@ EXPORT void orc_alimiter(const int16_t *x, int64_t n, int fs, int channels,
         for (int c = 0; c < channels; c++) peak = fmax(peak, fabs(buf[c]));
         att += delta;
         for (int c = 0; c < channels; c++) dst[c] = buf[c] * att;
+        if (att_out) att_out[nn] = att;
         if ((pos + channels) % buffer_size == nextpos[nextiter]) {
             delta = nextdelta[nextiter];
             att = limit / peak;
@@ -1092,6 +1093,22 @@ EXPORT void orc_alimiter(const int16_t *x, int64_t n, int fs, int channels,
     free(buffer);
     free(nextdelta);
     free(nextpos);
+}
+
+EXPORT void orc_alimiter(const int16_t *x, int64_t n, int fs, int channels,
+                         double level_in, double level_out, double limit,
+                         double attack_ms, double release_ms, int auto_level,
+                         int16_t *out) {
+    alimiter_core(x, n, fs, channels, level_in, level_out, limit, attack_ms, release_ms, auto_level, out, NULL);
+}
+
+/* orc_alimiter, and per frame the att that multiplies that frame's delayed samples
+ * (the value right after att += delta): att_out[n] doubles */
+EXPORT void orc_alimiter_trace(const int16_t *x, int64_t n, int fs, int channels,
+                               double level_in, double level_out, double limit,
+                               double attack_ms, double release_ms, int auto_level,
+                               int16_t *out, double *att_out) {
+    alimiter_core(x, n, fs, channels, level_in, level_out, limit, attack_ms, release_ms, auto_level, out, att_out);
 }
 
 /* loudnorm LINEAR mode (af_loudnorm.c, pass 2 at :240 when the measured values

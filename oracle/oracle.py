@@ -392,14 +392,21 @@ def kweight_coefs(fs):
 
 
 def alimiter(x16, fs, level_in=1.0, level_out=1.0, limit=0.98, attack=5.0, release=50.0,
-             auto_level=True):
+             auto_level=True, trace=False):
+    """af_alimiter on int16 [n, C].  trace=True: (y, att) with att float64 [n], per frame
+    the gain that multiplies that frame's delayed samples (orc_alimiter_trace)."""
     x16 = np.ascontiguousarray(x16, np.int16)
     out = np.empty_like(x16)
-    lib().orc_alimiter(_p(x16, _i16p), _i64(x16.shape[0]), ctypes.c_int(fs),
-                       ctypes.c_int(x16.shape[1]), ctypes.c_double(level_in),
-                       ctypes.c_double(level_out), ctypes.c_double(limit),
-                       ctypes.c_double(attack), ctypes.c_double(release),
-                       ctypes.c_int(1 if auto_level else 0), _p(out, _i16p))
+    args = (_p(x16, _i16p), _i64(x16.shape[0]), ctypes.c_int(fs),
+            ctypes.c_int(x16.shape[1]), ctypes.c_double(level_in),
+            ctypes.c_double(level_out), ctypes.c_double(limit),
+            ctypes.c_double(attack), ctypes.c_double(release),
+            ctypes.c_int(1 if auto_level else 0), _p(out, _i16p))
+    if trace:
+        att = np.ones(x16.shape[0], np.float64)
+        lib().orc_alimiter_trace(*args, _p(att, _f64p))
+        return out, att
+    lib().orc_alimiter(*args)
     return out
 
 
@@ -418,10 +425,13 @@ def loudness_stats(hist, st_hist):
     return float(out[0]), float(out[1]), float(out[2])
 
 
-def loudnorm_measure(x16, fs, native=False):
+def loudnorm_measure(x16, fs, native=False, measured=None):
     """pass-1 JSON 'input_*' strings: ffmpeg measures the track resampled to 192 kHz
-    (amx_oracle.c orc_ebur128_192k); native=True measures at the track's own rate."""
-    hist, st, peak, _ = ebur128(x16, fs) if native else ebur128_192k(x16, fs)
+    (amx_oracle.c orc_ebur128_192k); native=True measures at the track's own rate.
+    measured: that measurement's (hist, st_hist, peak, n_blocks) when the caller has it."""
+    if measured is None:
+        measured = ebur128(x16, fs) if native else ebur128_192k(x16, fs)
+    hist, st, peak, _ = measured
     I, lra, thr = loudness_stats(hist, st)
     tp = float(peak.max()) if peak.size else 0.0
     tp_db = 20.0 * np.log10(tp) if tp > 0 else -np.inf

@@ -355,17 +355,25 @@ def test_graph_replay_matches_eager(gpu, oracle_mod, settings):
     buffer's contents change (the graph holds pointers, not values)."""
     import torch
     from amx import synth
+    from amx.chunking import chunk_bounds, packet_frames
     from amx.engine import MasteringJob
     fs = 48000
     n = fs * 12
     xs = [synth.mix_like(n, fs, 2, seed=s) for s in (21, 22)]
     job = MasteringJob(fs, 2, settings, [n])
+    bounds = chunk_bounds(n, fs, packet_frames(2 * 4))       # a float32 stereo file's packets
+    assert bounds == [(s, m) for _, s, m in job.chunks]
+    refs = [oracle_mod.pipeline(oracle_mod.quantize(x), fs, settings, bounds) for x in xs]
+    assert [info["mode"] for _, info in refs] == ["linear", "linear"]
     d_in = torch.from_numpy(xs[0]).cuda()
     eager = job.run(d_in).cpu().numpy()
     job.capture(d_in)
-    np.testing.assert_array_equal(job.replay().cpu().numpy(), eager)
+    y0 = job.replay().cpu().numpy()
+    np.testing.assert_array_equal(y0, eager)
+    _cmp(y0, refs[0][0], "graph replay")
     d_in.copy_(torch.from_numpy(xs[1]))
     y = job.replay().cpu().numpy()
+    _cmp(y, refs[1][0], "graph replay, new input")
     eager2 = MasteringJob(fs, 2, settings, [n]).run(torch.from_numpy(xs[1]).cuda()).cpu().numpy()
     np.testing.assert_array_equal(y, eager2)
 

@@ -196,6 +196,31 @@ def test_alimiter_limits_peaks(oracle_mod):
     assert np.abs(y[-fs // 4:].astype(np.int32)).max() < np.abs(x[-fs // 4:].astype(np.int32)).max() / 0.98
 
 
+@pytest.mark.parametrize("C", [2, 5])
+def test_alimiter_trace_reproduces_output(oracle_mod, C):
+    """alimiter(trace=True): att[f] is the gain of frame f's delayed samples, so the
+    delayed input x trace, clamped to the limit, scaled and rounded in numpy is
+    orc_alimiter's int16 output; the traced call's output is the untraced one's"""
+    fs = 48000
+    n = int(fs * 1.5) + 1
+    t = np.arange(n)[:, None] / fs
+    c = np.arange(C)[None, :]
+    # amplitude-modulated sines whose peaks wander about the limit (0.98)
+    x = np.sin(2 * np.pi * (97 + 31 * c) * t + c) * (0.93 + 0.07 * np.sin(2 * np.pi * (3.1 + c) * t))
+    x16 =np.clip(np.round(x * 32767), -32768, 32767).astype(np.int16)
+    y = oracle_mod.alimiter(x16, fs)
+    y2, att = oracle_mod.alimiter(x16, fs, trace=True)
+    np.testing.assert_array_equal(y2, y)
+    assert att.shape == (n,) and att.dtype == np.float64
+    assert att.min() > 0.0          # right after att += delta: may pass 1 before the clamp
+    assert (att < 1.0).mean() >= 0.05, "the limiter must engage"
+    B = int(fs * 0.005)
+    d = np.zeros((n, C), np.float64)
+    d[B - 1:] = x16[:n - (B - 1)].astype(np.float64) * (1.0 / 32768.0)
+    v = np.clip(d * att[:, None], -0.98, 0.98) * (1 / 0.98) * 1.0
+    np.testing.assert_array_equal(np.clip(np.rint(v * 32768.0), -32768, 32767).astype(np.int16), y)
+
+
 # ------------------------------------------------- 192 kHz measurement (pass 1)
 def _py_swr_bank(fs, out_rate=192000):
     """Independent Python restatement of libswresample build_filter (Kaiser, factor
