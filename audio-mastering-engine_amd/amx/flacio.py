@@ -1,9 +1,14 @@
-"""FLAC input (the GUI's *.flac, mastering_gui.py:170; ffmpeg decodes it at :178).
+"""FLAC input (the GUI's *.flac, mastering_gui.py:170; ffmpeg decodes it at :178) and FLAC
+output (an output_file named *.flac, which ffmpeg's last command writes as FLAC, :223).
 
 The bitstream is decoded by libamx's host decoder (amx_flac_decode, csrc/amx_flac.cpp:
 frames decoded on a thread pool) into int32 samples left-justified to 32 bits -- the
 value ffmpeg's FLAC decoder hands on -- so the file reaches the device decode as s32
 PCM (amx_pcm_to_s16: >> 16, what the segment muxer's s16 WAV chunks hold).
+
+The write side encodes on the device (amx_flac_encode, csrc/amx_flacenc.hip): the int16
+master stays where the limiter left it, only the encoded frames cross the bus, and the
+host adds the 42 bytes in front of them (flac_container).
 """
 import ctypes
 
@@ -93,3 +98,94 @@ def read_flac_raw(path):
     WavInfo with packet_starts)"""
     x, fmt = read_flac_native(path)
     return np.ascontiguousarray(x).view(np.uint8).reshape(-1), fmt, "s32"
+
+
+def flac_container(payload, frame_bytes, fs, channels, total_frames, block, md5=None):
+    """FLAC file bytes: 'fLaC', one STREAMINFO block marked last, then the frame stream
+    `payload` (bytes-like).  frame_bytes: every frame's length (STREAMINFO's min / max frame
+    size); block: the fixed block size (the minimum too, unless the stream is one shorter
+    frame); md5: the 16-byte MD5 of the little-endian interleaved samples, or None for
+    zeros ("unknown", RFC 9639 8.2).  Pure host code."""
+    fb = np.asarray(frame_bytes, np.int64).reshape(-1)
+    total_frames, block = int(total_frames), int(block)
+    if not 1 <= channels <= 8 or not 1 <= fs <= 1048575 or not 16 <= block <= 65535:
+        raise ValueError("flac_container: channels 1..8, rate 1..1048575, block 16..65535")
+    if md5 is None:
+        md5 = bytes(16)
+    if len(md5) != 16:
+        raise ValueError("flac_container: md5 must be 16 bytes")
+    if fb.size != (total_frames + block - 1) // block:
+        raise ValueError("flac_container: %d frame lengths for %d samples in blocks of %d"
+                         % (fb.size, total_frames, block))
+    max_block = block if fb.size != 1 else total_frames
+    min_block = max_block if fb.size <= 1 else block
+    min_frame = int(fb.min()) if fb.size else 0
+    max_frame = int(fb.max()) if fb.size else 0
+    if max_frame >= 1 << 24:
+        min_frame = max_frame = 0                      # "unknown": the field holds 24 bits
+    v = min_block
+    for value, bits in ((max_block, 16), (min_frame, 24), (max_frame, 24), (int(fs), 20),
+                        (channels - 1, 3), (16 - 1, 5), (total_frames, 36)):
+        v = (v << bits) | (int(value) & ((1 << bits) - 1))
+    head = b"fLaC" + bytes([0x80]) + (34).to_bytes(3, "big") + v.to_bytes(18, "big") + bytes(md5)
+    return head + bytes(payload)
+
+
+def encode_flac_device(d_pcm16, fs, block=4096, sub_bits=False):
+    """The FLAC frame stream of a device int16 tensor [frames, channels] (or [frames]),
+    encoded on the device: (payload uint8 device tensor, frame lengths int32 device tensor);
+    with sub_bits also the chosen subframes' sizes in bits, int32 [n_frames, channels]."""
+    import torch
+    x = d_pcm16
+    if x.dtype != torch.int16 or not x.is_cuda:
+        raise ValueError("encode_flac_device takes an int16 tensor on the device")
+    if x.dim() == 1:
+        x = x[:, None]
+    x = x.contiguous()
+    frames, channels = int(x.shape[0]), int(x.shape[1])
+    L = capi.load()
+    nf, cap, wsb = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+    capi.check(L.amx_flac_encode_size(frames, channels, int(block), ctypes.byref(nf), ctypes.byref(cap),
+                                      ctypes.byref(wsb)), "amx_flac_encode_size")
+    dev = x.device
+    out = torch.empty(cap.value, dtype=torch.uint8, device=dev)
+    fbytes = torch.empty(nf.value, dtype=torch.int32, device=dev)
+    sb = torch.empty((nf.value, channels), dtype=torch.int32, device=dev) if sub_bits else None
+    total = torch.empty(1, dtype=torch.int64, device=dev)
+    ws = torch.empty((wsb.value + 7) // 8, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        capi.check(L.amx_flac_encode(capi.ptr(x), frames, channels, int(fs), int(block), capi.ptr(out), cap.value,
+                                     capi.ptr(fbytes), capi.ptr(sb), capi.ptr(total), capi.ptr(ws), ws.numel() * 8,
+                                     capi.ptr_stream()), "amx_flac_encode")
+        n = int(total.item())
+    if sub_bits:
+        return out[:n], fbytes, sb
+    return out[:n], fbytes
+
+
+def flac_bytes(x16, fs, block=4096, md5=True):
+    """The FLAC file of int16 samples [frames, channels] (a device tensor or a numpy array)."""
+    import hashlib
+    import torch
+    if isinstance(x16, np.ndarray):
+        x16 = torch.from_numpy(np.ascontiguousarray(x16, np.int16))
+    if x16.dim() == 1:
+        x16 = x16[:, None]
+    frames, channels = int(x16.shape[0]), int(x16.shape[1])
+    if frames == 0:
+        # nothing to encode: STREAMINFO alone (the MD5 of no samples)
+        return flac_container(b"", [], fs, channels, 0, block, hashlib.md5(b"").digest() if md5 else None)
+    digest = None
+    if md5:
+        # the host hashes the raw PCM: the D2H of the samples the encoder otherwise saves
+        digest = hashlib.md5(x16.cpu().contiguous().numpy().astype("<i2", copy=False).tobytes()).digest()
+    payload, fbytes = encode_flac_device(x16.to("cuda"), fs, block)
+    return flac_container(payload.cpu().numpy().tobytes(), fbytes.cpu().numpy(), fs, channels, frames, block, digest)
+
+
+def write_flac(path, x16, fs, block=4096, md5=True):
+    """x16 int16 [frames, channels] (device tensor or numpy array) as a 16-bit FLAC file.
+    md5=False leaves STREAMINFO's MD5 zero and moves only the encoded bytes off the device."""
+    data = flac_bytes(x16, fs, block, md5)
+    with open(path, "wb") as f:
+        f.write(data)

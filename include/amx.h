@@ -46,8 +46,10 @@ extern "C" {
 /* ABI history.  3 -> 4 (round 6): amx_loudnorm_desc gained reuse_stream (the struct
  * grew), amx_ln_shard.pad_ became `windowed`, d_edge went from [2][16][2] to [2][80][2]
  * frames per track, amx_final_desc.pad_ became `from_rest`.  A caller built against
- * an older header must be rebuilt: amx_abi_version() tells it which layout it gets. */
-#define AMX_ABI_VERSION 4
+ * an older header must be rebuilt: amx_abi_version() tells it which layout it gets.
+ * 4 -> 5: amx_flac_encode_size and amx_flac_encode added (the FLAC output); no layout
+ * of an existing structure changed. */
+#define AMX_ABI_VERSION 5
 
 #if defined(__GNUC__)
 #define AMX_API __attribute__((visibility("default")))
@@ -242,6 +244,30 @@ AMX_API int amx_flac_info(const uint8_t *data, int64_t size, amx_flac_info_t *in
 AMX_API int amx_flac_decode(const uint8_t *data, int64_t size, int32_t *out, int64_t out_frames,
                             int64_t *frames_out, int32_t threads, int32_t *blocks, int64_t max_blocks,
                             int64_t *n_blocks);
+
+/* (ABI 5) FLAC output (:223 writes output_file with the container its extension names;
+ * a .flac master).  The encoder runs on the device: d_pcm int16 [frames][channels]
+ * interleaved (channels 1..8) -> a fixed-blocksize FLAC frame stream (RFC 9639; frames of
+ * `block` samples, 16..4608, and a shorter last one) written back to back into d_out.
+ * Search space, exact: per subframe CONSTANT, VERBATIM or FIXED order
+ * 0..4 with Rice coding method 0 (k 0..14, no escapes), partition order 0..min(6,
+ * trailing zero bits of the frame's block size); stereo takes the smallest of the four
+ * channel assignments.  No metadata is written: the host prepends "fLaC" + STREAMINFO
+ * (amx/flacio.py flac_container).
+ * amx_flac_encode_size: the frame count, the d_out capacity amx_flac_encode asks for (every
+ * frame at its VERBATIM bound) and the workspace bytes.
+ * amx_flac_encode: d_frame_bytes u32 [n_frames] = each frame's length in bytes,
+ * d_sub_bits u32 [n_frames][channels] = the chosen subframes' sizes in bits (may be
+ * NULL), d_total_bytes = the stream's length.  Kernels only, no host synchronisation.
+ * Errors: AMX_EINVAL (channels outside 1..8, frames < 1, a null pointer), AMX_ERANGE
+ * (block outside 16..4608, sample_rate outside 1..1048575, out_capacity or
+ * workspace_bytes below amx_flac_encode_size's). */
+AMX_API int amx_flac_encode_size(int64_t frames, int32_t channels, int32_t block, int64_t *n_frames,
+                                 int64_t *max_out_bytes, int64_t *workspace_bytes);
+AMX_API int amx_flac_encode(const int16_t *d_pcm, int64_t frames, int32_t channels, int32_t sample_rate,
+                            int32_t block, uint8_t *d_out, int64_t out_capacity, uint32_t *d_frame_bytes,
+                            uint32_t *d_sub_bits, int64_t *d_total_bytes, void *workspace,
+                            int64_t workspace_bytes, void *stream);
 
 /* Diagnostics of the compressor envelope's fix-up (AMX_STAGE_FIX) of the last step run
  * on d_ws: out[0..3] = segments the chain walkers re-ran, the longest walk (segments one
