@@ -104,7 +104,7 @@ def flac_container(payload, frame_bytes, fs, channels, total_frames, block, md5=
     """FLAC file bytes: 'fLaC', one STREAMINFO block marked last, then the frame stream
     `payload` (bytes-like).  frame_bytes: every frame's length (STREAMINFO's min / max frame
     size); block: the fixed block size (the minimum too, unless the stream is one shorter
-    frame); md5: the 16-byte MD5 of the little-endian interleaved samples, or None for
+    frame: then both fields hold its length, but no less than 16); md5: the 16-byte MD5 of the little-endian interleaved samples, or None for
     zeros ("unknown", RFC 9639 8.2).  Pure host code."""
     fb = np.asarray(frame_bytes, np.int64).reshape(-1)
     total_frames, block = int(total_frames), int(block)
@@ -117,7 +117,8 @@ def flac_container(payload, frame_bytes, fs, channels, total_frames, block, md5=
     if fb.size != (total_frames + block - 1) // block:
         raise ValueError("flac_container: %d frame lengths for %d samples in blocks of %d"
                          % (fb.size, total_frames, block))
-    max_block = block if fb.size != 1 else total_frames
+    # (RFC 9639 8.2: both block sizes lie in 16..65535, also for one frame of 1..15 samples)
+    max_block = block if fb.size != 1 else max(16, total_frames)
     min_block = max_block if fb.size <= 1 else block
     min_frame = int(fb.min()) if fb.size else 0
     max_frame = int(fb.max()) if fb.size else 0

@@ -214,7 +214,8 @@ __host__ __device__ static inline int fe_rate_code(int fs, int *extra_bytes, int
     default: break;
     }
     if (fs < 65536) { *extra_bytes = 2; *extra_val = fs; return 13; }
-    if (fs % 10 == 0 && fs / 10 < 65536) { *extra_bytes = 2; *extra_val = fs / 10; return 14; }
+    // (below 655 350: tens of Hz up to 65 534, the all-ones value is left alone)
+    if (fs % 10 == 0 && fs < 655350) { *extra_bytes = 2; *extra_val = fs / 10; return 14; }
     return 0;
 }
 __host__ __device__ static inline int fe_block_code(int n, int *extra_bytes) {

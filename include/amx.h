@@ -259,7 +259,10 @@ AMX_API int amx_flac_decode(const uint8_t *data, int64_t size, int32_t *out, int
  * amx_flac_encode: d_frame_bytes u32 [n_frames] = each frame's length in bytes,
  * d_sub_bits u32 [n_frames][channels] = the chosen subframes' sizes in bits (may be
  * NULL), d_total_bytes = the stream's length.  Kernels only, no host synchronisation.
- * Errors: AMX_EINVAL (channels outside 1..8, frames < 1, a null pointer), AMX_ERANGE
+ * workspace must be 8-byte aligned (it starts with the frames' int64 offsets); d_out may
+ * have any alignment.
+ * Errors: AMX_EINVAL (channels outside 1..8, frames < 1, a null pointer, a workspace that
+ * is not 8-byte aligned), AMX_ERANGE
  * (block outside 16..4608, sample_rate outside 1..1048575, out_capacity or
  * workspace_bytes below amx_flac_encode_size's). */
 AMX_API int amx_flac_encode_size(int64_t frames, int32_t channels, int32_t block, int64_t *n_frames,

@@ -270,8 +270,9 @@ def encode(x, fs, bps, seed=0, block=4096, variable=False, kinds=None, assigns=N
         fno += 1
     # metadata: STREAMINFO (+ PADDING and an APPLICATION block)
     si = BitWriter()
-    si.put(min(sizes) if len(sizes) > 1 else sizes[0], 16)
-    si.put(max(sizes), 16)
+    # (RFC 9639 8.2: the minimum leaves the last block out, and both fields lie in 16..65535)
+    si.put(max(16, min(sizes[:-1]) if len(sizes) > 1 else sizes[0]), 16)
+    si.put(max(16, max(sizes)), 16)
     si.put(min(len(f) for f in frames), 24)
     si.put(max(len(f) for f in frames), 24)
     si.put(fs, 20)

@@ -5,8 +5,19 @@ The encoder is pinned three ways: the in-tree decoder (amx_flac_decode, itself p
 tests/flac_enc.py) must give the samples back bit for bit; every subframe's size must
 EQUAL the minimum a brute-force numpy search finds over the encoder's search space
 (the search space is the specification, so this is an equality); and the
-container's sizes, MD5 and argument errors are checked directly.  No third-party FLAC
-implementation is involved.
+container's sizes, MD5 and argument errors are checked directly.
+
+Every stream also goes through tests/flac_verify.py, a strict reader written from RFC 9639
+alone that shares no code with the in-tree decoder, with profile=True (the encoder's own
+promises): that pins what amx_flac_decode skips or accepts either way -- the
+coded frame number and its shortest coding, the rate, sample-size and block-size codes and
+their extra bytes against STREAMINFO, the blocking strategy, the reserved and padding bits,
+STREAMINFO's block and frame sizes, and that each frame starts where the lengths the encoder
+reports say (the placement scan over more than 1024 frames, 3- and 4-byte frame numbers).
+The direct C ABI tests hold the encoder to its buffers: canaries behind the stream and the
+arrays, buffers reused without clearing, an output pointer at any alignment.  What is still
+not pinned: no third-party FLAC implementation is involved, so the reader and the encoder
+share one person's reading of the RFC.
 """
 import ctypes
 import hashlib
@@ -15,6 +26,8 @@ import tempfile
 
 import numpy as np
 import pytest
+
+import flac_verify
 
 pytestmark = pytest.mark.gpu
 
@@ -92,12 +105,26 @@ def _info(data):
     return fi
 
 
+def _check_format(x16, data, fb, frames=None):
+    """the independent reader on one encode: the stream keeps RFC 9639 and the encoder's
+    profile, every frame starts where the reported lengths say, and the samples are the
+    input's (frames: decode only these frames fully, tests/flac_verify.py)"""
+    got, rep = flac_verify.verify(data, profile=True, frames=frames, frame_bytes=fb)
+    if frames is None:
+        np.testing.assert_array_equal(got, x16.astype(np.int64))
+        assert rep["md5_checked"]
+    assert [f["number"] for f in rep["frames"]] == list(range(len(fb)))
+    assert [f["length"] for f in rep["frames"]] == [int(v) for v in fb]
+    return got, rep
+
+
 def _check_stream(x16, fs, block, data, fb, sb):
     """round trip, sizes and the exact optimum of one encode"""
     from amx import flacio
     frames, C = x16.shape
     got, _ = flacio.decode_flac(data)
     np.testing.assert_array_equal(got, x16.astype(np.int32) << 16)
+    _check_format(x16, data, fb)
     fi = _info(data)
     assert (fi.sample_rate, fi.channels, fi.bits_per_sample, fi.total_frames) == (fs, C, 16, frames)
     # sizes
@@ -322,3 +349,226 @@ def test_master_audio_writes_flac(gpu, kind, flac_name, out_fs):
     assert fi.total_frames == y.shape[0] > 0
     np.testing.assert_array_equal(got, y.astype(np.int32).reshape(got.shape) << 16)
     assert data[26:42] == hashlib.md5(np.ascontiguousarray(y, "<i2").tobytes()).digest()
+
+
+# ------------------------------------------------------------------ 9: the placement scan's passes
+@pytest.mark.parametrize("C,nf,tail", [(2, 1023, 0), (2, 1024, 0), (2, 1025, 0), (2, 2049, 0), (1, 1025, 0),
+                                       (8, 1025, 5)])
+def test_placement_passes(gpu, C, nf, tail):
+    """k_flac_place scans 1024 frame lengths at a time and carries the sum: frame counts
+    around one and two passes, music so that the lengths vary and the offsets land on every
+    alignment.  tail: the last of the nf frames holds 5 samples."""
+    from amx import flacio
+    block = 16
+    frames = block * nf if not tail else block * (nf - 1) + tail
+    x = _music(frames, C, 48000, seed=nf + C)
+    data, fb, sb = _encode(x, 48000, block)
+    assert len(fb) == nf and int(fb.astype(np.int64).sum()) == len(data) - 42
+    assert len(set(int(v) for v in fb)) > 1
+    offs = 42 + np.concatenate([[0], np.cumsum(fb.astype(np.int64))[:-1]])
+    assert set(int(o) & 3 for o in offs) == {0, 1, 2, 3}
+    assert all(data[o] == 0xFF and data[o + 1] == 0xF8 for o in offs)
+    _check_format(x, data, fb)
+    got, _ = flacio.decode_flac(data)
+    np.testing.assert_array_equal(got, x.astype(np.int32) << 16)
+
+
+# ------------------------------------------------------------------ 10: 3- and 4-byte frame numbers
+def test_long_numbering(gpu):
+    """65 537 frames (mono, block 16, a last frame of 5 samples): frame numbers of 1 to 4
+    bytes and 65 passes of the placement scan.  The reader checks every header and steps by
+    the reported lengths; it decodes the frames around each change of the number's length."""
+    from amx import flacio
+    block, frames = 16, 16 * 65536 + 5
+    m = _music(65536, 1, 48000, seed=21)
+    x = np.ascontiguousarray(np.concatenate([m] * 16 + [m[:5]]))
+    assert x.shape == (frames, 1)
+    data, fb, sb = _encode(x, 48000, block)
+    assert len(fb) == 65537 and int(fb.astype(np.int64).sum()) == len(data) - 42
+    got, _ = flacio.decode_flac(data)
+    np.testing.assert_array_equal(got, x.astype(np.int32) << 16)
+    full = sorted(set(k + d for k in (0, 127, 128, 2047, 2048, 65535, 65536) for d in (-1, 0, 1)
+                      if 0 <= k + d <= 65536))
+    part, rep = _check_format(x, data, fb, frames=full)
+    for k in full:
+        assert rep["frames"][k]["decoded"]
+        np.testing.assert_array_equal(part[k * block:(k + 1) * block], x[k * block:(k + 1) * block].astype(np.int64))
+    assert [rep["frames"][k]["number_bytes"] for k in (0, 127, 128, 2047, 2048, 65535, 65536)] == [1, 1, 2, 2, 3, 3, 4]
+    assert rep["frames"][65536]["block"] == 5
+
+
+# ------------------------------------------------------------------ 11: sample-rate codes
+RATE_CODES = {8000: 4, 16000: 5, 22050: 6, 24000: 7, 32000: 8, 88200: 1, 176400: 2, 352800: 14, 384000: 14,
+              655350: 0, 65535: 13, 65536: 0, 1048575: 0}
+
+
+@pytest.mark.parametrize("fs", list(RATE_CODES))
+def test_rate_codes(gpu, fs):
+    """table rates, Hz in 16 bits (up to 65 535), tens of Hz in 16 bits (below 655 350), and
+    the rates only STREAMINFO can hold (code 0)"""
+    block, frames = 1152, 3 * 1152 + 100
+    x = _music(frames, 2, 48000, seed=31)
+    data, fb, sb = _encode(x, fs, block)
+    _check_stream(x, fs, block, data, fb, sb)
+    rep = flac_verify.verify(data, profile=True)[1]
+    assert rep["sample_rate"] == fs and [f["rate_code"] for f in rep["frames"]] == [RATE_CODES[fs]] * 4
+
+
+# ------------------------------------------------------------------ 12: block-size codes
+BLOCK_CODES = {192: 1, 576: 2, 2304: 4, 256: 8, 512: 9, 2048: 11, 255: 6, 257: 7, 4607: 7}
+
+
+@pytest.mark.parametrize("block", list(BLOCK_CODES))
+def test_block_size_codes(gpu, block):
+    tail = 37
+    x = _music(block + tail, 1, 48000, seed=41)
+    data, fb, sb = _encode(x, 48000, block)
+    _check_stream(x, 48000, block, data, fb, sb)
+    rep = flac_verify.verify(data, profile=True)[1]
+    assert [(f["block"], f["block_code"]) for f in rep["frames"]] == [(block, BLOCK_CODES[block]), (tail, 6)]
+
+
+# ------------------------------------------------------------------ 13: the side channel's extremes
+def _extremes(n):
+    t = np.arange(n)
+    hi, lo = np.full(n, 32767, np.int16), np.full(n, -32768, np.int16)
+    alt = np.where(t % 2 == 0, 32767, -32768).astype(np.int16)
+    neg = np.where(t % 2 == 0, -32768, 32767).astype(np.int16)
+    return {"side_max": np.stack([hi, lo], axis=1), "side_min": np.stack([lo, hi], axis=1),
+            "alternating_opposed": np.stack([alt, neg], axis=1), "both_min": np.stack([lo, lo], axis=1)}
+
+
+@pytest.mark.parametrize("block", [4096, 1000])
+@pytest.mark.parametrize("name", ["side_max", "side_min", "alternating_opposed", "both_min"])
+def test_side_channel_extremes(gpu, name, block):
+    """one block of L - R = +-65535 (17 bits), of L and R alternating between the extremes in
+    opposition (the order-4 residual of the side channel at its largest), of L = R = -32768"""
+    x = np.ascontiguousarray(_extremes(block)[name])
+    data, fb, sb = _encode(x, 48000, block)
+    _check_stream(x, 48000, block, data, fb, sb)
+
+
+# ------------------------------------------------------------------ 14-17: the C ABI's buffers
+SENTINEL = -7
+
+
+class _Raw:
+    """amx_flac_encode through the C ABI on buffers the test owns: d_out of the asked
+    capacity inside an allocation with `spare` bytes of 0x55 behind it (and out_shift bytes
+    before it), d_frame_bytes and d_sub_bits with 8 spare entries of SENTINEL"""
+
+    def __init__(self, frames, C, block, spare=64, out_shift=0):
+        import torch
+        from amx import capi
+        self.L, self.capi, self.torch = capi.load(), capi, torch
+        nf, cap, wsb = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+        assert self.L.amx_flac_encode_size(frames, C, block, ctypes.byref(nf), ctypes.byref(cap),
+                                           ctypes.byref(wsb)) == capi.AMX_OK
+        self.frames, self.C, self.block, self.nf, self.cap, self.shift = frames, C, block, nf.value, cap.value, out_shift
+        self.store = torch.full((out_shift + cap.value + spare,), 0x55, dtype=torch.uint8, device="cuda")
+        self.fb = torch.full((nf.value + 8,), SENTINEL, dtype=torch.int32, device="cuda")
+        self.sb = torch.full((nf.value * C + 8,), SENTINEL, dtype=torch.int32, device="cuda")
+        self.total = torch.full((1,), SENTINEL, dtype=torch.int64, device="cuda")
+        self.ws = torch.full(((wsb.value + 7) // 8 + 1,), SENTINEL, dtype=torch.int64, device="cuda")
+
+    def encode(self, x16, fs, ws_shift=0):
+        """(rc, stream bytes up to total or None)"""
+        torch, capi = self.torch, self.capi
+        d = torch.from_numpy(np.ascontiguousarray(x16)).cuda()
+        assert d.shape == (self.frames, self.C)
+        ws = ctypes.c_void_p(self.ws.data_ptr() + ws_shift)
+        rc = self.L.amx_flac_encode(capi.ptr(d), self.frames, self.C, fs, self.block, capi.ptr(self.store[self.shift:]),
+                                    self.cap, capi.ptr(self.fb), capi.ptr(self.sb), capi.ptr(self.total), ws,
+                                    self.ws.numel() * 8 - 8, capi.ptr_stream())
+        torch.cuda.synchronize()
+        if rc != capi.AMX_OK:
+            return rc, None
+        n = int(self.total.item())
+        assert 0 < n <= self.cap
+        return rc, self.store[self.shift:self.shift + n].cpu().numpy().tobytes()
+
+    def untouched_beyond(self, n):
+        """every byte of the allocation before d_out and from d_out + n on, and every spare
+        entry, is as it was filled"""
+        store = self.store.cpu().numpy()
+        assert (store[:self.shift] == 0x55).all() and (store[self.shift + n:] == 0x55).all()
+        assert bool((self.fb[self.nf:] == SENTINEL).all()) and bool((self.sb[self.nf * self.C:] == SENTINEL).all())
+
+    def file(self, x16, fs, payload):
+        from amx import flacio
+        md5 = hashlib.md5(np.ascontiguousarray(x16, "<i2").tobytes()).digest()
+        fb = self.fb[:self.nf].cpu().numpy()
+        return flacio.flac_container(payload, fb, fs, self.C, self.frames, self.block, md5), fb
+
+
+FRAMES_ABI, BLOCK_ABI = 3 * 4096 + 1000, 4096
+
+
+def test_canaries(gpu):
+    """a successful encode writes d_out[0, total), d_frame_bytes[0, n_frames) and
+    d_sub_bits[0, n_frames * channels) and nothing else"""
+    x = _music(FRAMES_ABI, 2, 48000, seed=51)
+    raw = _Raw(FRAMES_ABI, 2, BLOCK_ABI)
+    rc, payload = raw.encode(x, 48000)
+    assert rc == raw.capi.AMX_OK
+    raw.untouched_beyond(len(payload))
+    data, fb = raw.file(x, 48000, payload)
+    assert int(fb.astype(np.int64).sum()) == len(payload)
+    _check_format(x, data, fb)
+    sb = raw.sb[:raw.nf * 2].cpu().numpy().reshape(raw.nf, 2)
+    _check_stream(x, 48000, BLOCK_ABI, data, fb, sb)
+
+
+def test_reuse_without_clearing(gpu):
+    """the same d_out, workspace, d_frame_bytes and d_total_bytes for full-scale noise (the
+    largest frames), silence (the smallest) and music, nothing cleared in between: each
+    stream is the input's (the reader) and equals the one encoded into fresh buffers"""
+    rng = np.random.default_rng(61)
+    inputs = [rng.integers(-32768, 32768, (FRAMES_ABI, 2)).astype(np.int16), np.zeros((FRAMES_ABI, 2), np.int16),
+              _music(FRAMES_ABI, 2, 48000, seed=62)]
+    used = _Raw(FRAMES_ABI, 2, BLOCK_ABI)
+    sizes = []
+    for x in inputs:
+        rc, payload = used.encode(x, 48000)
+        assert rc == used.capi.AMX_OK
+        data, fb = used.file(x, 48000, payload)
+        _check_format(x, data, fb)
+        fresh = _Raw(FRAMES_ABI, 2, BLOCK_ABI)
+        rc, want = fresh.encode(x, 48000)
+        assert rc == used.capi.AMX_OK and payload == want
+        np.testing.assert_array_equal(fb, fresh.fb[:fresh.nf].cpu().numpy())
+        np.testing.assert_array_equal(used.sb.cpu().numpy(), fresh.sb.cpu().numpy())
+        sizes.append(len(payload))
+    assert sizes[0] > sizes[2] > sizes[1]
+    used.untouched_beyond(sizes[0])            # the largest of the three reached this far, none further
+
+
+@pytest.mark.parametrize("shift", [1, 2, 3])
+def test_output_pointer_at_any_alignment(gpu, shift):
+    """d_out + shift inside a larger allocation: the same stream as at an aligned address,
+    and not a byte before d_out or from d_out + total on"""
+    x = _music(FRAMES_ABI, 2, 48000, seed=71)
+    aligned, moved = _Raw(FRAMES_ABI, 2, BLOCK_ABI), _Raw(FRAMES_ABI, 2, BLOCK_ABI, out_shift=shift)
+    assert moved.store.data_ptr() % 4 == 0
+    rc, want = aligned.encode(x, 48000)
+    assert rc == aligned.capi.AMX_OK
+    rc, payload = moved.encode(x, 48000)
+    assert rc == moved.capi.AMX_OK and payload == want
+    moved.untouched_beyond(len(payload))
+    data, fb = moved.file(x, 48000, payload)
+    _check_format(x, data, fb)
+
+
+def test_misaligned_workspace_is_refused(gpu):
+    """the workspace starts with the frames' int64 offsets: workspace + 4 is AMX_EINVAL,
+    refused on the host before anything is launched"""
+    x = _music(FRAMES_ABI, 2, 48000, seed=81)
+    raw = _Raw(FRAMES_ABI, 2, BLOCK_ABI)
+    rc, payload = raw.encode(x, 48000, ws_shift=4)
+    assert rc == raw.capi.AMX_EINVAL and payload is None
+    raw.untouched_beyond(0)
+    assert int(raw.total.item()) == SENTINEL and bool((raw.fb == SENTINEL).all()) and bool((raw.sb == SENTINEL).all())
+    assert bool((raw.ws == SENTINEL).all())
+    rc, payload = raw.encode(x, 48000)
+    assert rc == raw.capi.AMX_OK
+    _check_format(x, *raw.file(x, 48000, payload))
