@@ -7,6 +7,10 @@ Provenance: the SHA-256 of every source the library is compiled from
 (source_hash) is stamped into it (-DAMX_SRC_HASH, read back by amx_build_id).
 capi.load() recomputes the hash from the tree it runs in and refuses a library
 built from other sources, so a GPU run always executes the committed kernels.
+
+The host side is two sources: amx_plan_build.cpp builds a plan's tables from its
+arguments (no HIP in it; tests/test_plan_build.py also compiles it with the host
+compiler alone), amx_plan.cpp uploads them and holds the C ABI.
 """
 import hashlib
 import os
@@ -18,8 +22,8 @@ OUT = os.path.join(PKG, "lib", "libamx.so")
 HEADER = os.path.join(PKG, "..", "include", "amx.h")
 SOURCES = ["amx_chain.hip", "amx_scan.hip", "amx_dyn.hip", "amx_loud.hip", "amx_loud192.hip", "amx_final.hip", "amx_io.hip",
            "amx_loudnorm.hip", "amx_flacenc.hip",
-           "amx_plan.cpp", "amx_flac.cpp"]
-HEADERS = ["amx_internal.hpp", "amx_dev.hpp"]
+           "amx_plan.cpp", "amx_plan_build.cpp", "amx_flac.cpp"]
+HEADERS = ["amx_internal.hpp", "amx_dev.hpp", "amx_tables.hpp", "amx_plan_build.hpp", "amx_plan.hpp"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
          "-fvisibility=hidden", "-ffp-contract=off", "-Wall", "-Wno-unused-function"]
 

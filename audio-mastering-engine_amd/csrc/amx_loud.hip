@@ -346,8 +346,6 @@ hipError_t launch_hist(const SpanDev *spans, int n_tracks, int hop, const double
 // track, each workgroup reduces a contiguous run of that track's segments in LDS
 // and issues one atomicMax per channel (the peak buffer is zeroed by
 // amx_loudness_pass1 first): same-address atomics serialise, so there are few.
-#define AMX_PEAK_THREADS 1024
-#define AMX_PEAK_PER_THREAD 8
 // kw_fix: k_front2 accumulated the K-filter GEMV with the row of a full L-frame
 // segment (wave-uniform); a span's last segment shorter than L needs its rows
 // right-aligned (G[n + L - len], as k_kw1 does), so wave 0 of the span's first
@@ -474,11 +472,6 @@ __global__ void __launch_bounds__(AMX_PEAK_THREADS) k_peak_reduce(const SpanDev 
             cnt[t] = 0u;
         }
     }
-}
-
-int peak_reduce_blocks(int64_t max_nkseg) {
-    const int64_t per = (int64_t)AMX_PEAK_THREADS * AMX_PEAK_PER_THREAD;
-    return (int)((max_nkseg + per - 1) / per);
 }
 
 hipError_t launch_peak_reduce(const SpanDev *spans, int n_tracks, int64_t max_nkseg,

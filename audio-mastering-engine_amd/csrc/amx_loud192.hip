@@ -477,16 +477,6 @@ k_up_poly(UpArgs a) {
     acc_store(a, acc, j, ch);
 }
 
-// the (CMIN, CMAX, TB) forms k_up_poly is built for
-#define AMX_UP_POLY_FORMS(X) X(4, 5, 7) X(2, 3, 7) X(1, 2, 7) X(6, 6, 8) X(3, 3, 8)
-
-int up_poly_form(int cmin, int cmax, int tb) {
-#define AMX_UP_POLY_HAS(c0, c1, t) if (cmin == c0 && cmax == c1 && tb == t) return AMX_UP_POLY(c0, c1, t);
-    AMX_UP_POLY_FORMS(AMX_UP_POLY_HAS)
-#undef AMX_UP_POLY_HAS
-    return 0;
-}
-
 // The general kernel, over the plan's list of the segments k_up does not take (span
 // ends, partial segments, hop splits) -- or over every segment when the rate has no
 // unrolled form (M > 1, e.g. 44.1 kHz: phase pattern from the tables, the window

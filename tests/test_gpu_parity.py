@@ -482,7 +482,7 @@ def test_front1_variants_vs_oracle(gpu, oracle_mod, monkeypatch, env):
         "22k05-lin", "11k025-lin"])
 def test_loudness_192k_rates_vs_oracle(gpu, oracle_mod, monkeypatch, fs, env):
     """the 192 kHz measurement at the rates without the unrolled k_up: k_up_poly's forms
-    (amx_loud192.hip AMX_UP_POLY_FORMS) and k_up_slow (AMX_UP_POLY = 0, and 24 kHz, whose
+    (amx_tables.hpp AMX_UP_POLY_FORMS) and k_up_slow (AMX_UP_POLY = 0, and 24 kHz, whose
     form is not built; 22.05 / 11.025 kHz with libswresample's 1024-phase interpolating
     kernel, swr_dot_lin) -- histograms, 192 kHz sample peaks bit for bit, the statistics"""
     import torch

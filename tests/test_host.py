@@ -141,7 +141,7 @@ def test_reciprocal_division_is_ieee_quotient(tmp_path):
     FMA residual step (amx_dyn.hip env_div, gain_frame).  Markstein's theorem makes
     that the IEEE quotient for a correctly rounded 1/b; checked here on random and
     edge operands with the C library's fma (the plan additionally checks every
-    compressor table value, amx_plan.cpp env_rcp)."""
+    compressor table value, amx_plan_build.cpp env_rcp)."""
     import ctypes
     import subprocess
     import numpy as np
