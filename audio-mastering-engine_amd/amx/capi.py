@@ -14,7 +14,7 @@ c_double_p = ctypes.POINTER(ctypes.c_double)
 c_float_p = ctypes.POINTER(ctypes.c_float)
 
 AMX_OK, AMX_EINVAL, AMX_EHIP, AMX_ENOMEM, AMX_ERANGE = 0, -1, -2, -3, -4
-ABI_VERSION = 5
+ABI_VERSION = 6
 CTL_FAST = 1
 MODES = ("off", "skip", "linear", "dynamic")
 STATS = 16
@@ -110,7 +110,7 @@ EXPORTS = ("amx_abi_version", "amx_last_error", "amx_build_id", "amx_plan_create
            "amx_plan_set_limiter_channels",
            "amx_mc_plan_create", "amx_mc_plan_free", "amx_mc_plan_get_info", "amx_mc_run_chunks",
            "amx_mc_split_pairs", "amx_mc_loudness_combine", "amx_mc_peak_pick", "amx_mc_limiter_out",
-           "amx_flac_encode_size", "amx_flac_encode")
+           "amx_flac_encode_size", "amx_flac_encode", "amx_flac_encode_size_ex", "amx_flac_encode_ex")
 PCM_FORMATS = {"u8": 0, "s16": 1, "s24": 2, "s32": 3, "f32": 4, "f64": 5,
                "s8": 6, "s16be": 7, "s24be": 8, "s32be": 9, "f32be": 10, "f64be": 11}
 
@@ -191,6 +191,10 @@ def load(path=None):
         [ctypes.POINTER(ctypes.c_int64)] * 3
     L.amx_flac_encode.argtypes = [vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, vp,
                                   ctypes.c_int64, vp, vp, vp, vp, ctypes.c_int64, vp]
+    L.amx_flac_encode_size_ex.argtypes = [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32] + \
+        [ctypes.POINTER(ctypes.c_int64)] * 3
+    L.amx_flac_encode_ex.argtypes = [vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                     ctypes.c_int32, vp, ctypes.c_int64, vp, vp, vp, vp, ctypes.c_int64, vp]
     if L.amx_abi_version() != ABI_VERSION:
         raise AmxError("libamx ABI version mismatch")
     L.amx_build_id.restype = ctypes.c_char_p

@@ -132,11 +132,20 @@ def flac_container(payload, frame_bytes, fs, channels, total_frames, block, md5=
     return head + bytes(payload)
 
 
-def encode_flac_device(d_pcm16, fs, block=4096, sub_bits=False):
+def _lpc_order(lpc_order):
+    """lpc_order as an int in 0..8 (ValueError otherwise, before any device call)"""
+    if isinstance(lpc_order, bool) or not isinstance(lpc_order, (int, np.integer)) or not 0 <= lpc_order <= 8:
+        raise ValueError("lpc_order must be an int in 0..8, not %r" % (lpc_order,))
+    return int(lpc_order)
+
+
+def encode_flac_device(d_pcm16, fs, block=4096, sub_bits=False, lpc_order=0):
     """The FLAC frame stream of a device int16 tensor [frames, channels] (or [frames]),
     encoded on the device: (payload uint8 device tensor, frame lengths int32 device tensor);
-    with sub_bits also the chosen subframes' sizes in bits, int32 [n_frames, channels]."""
+    with sub_bits also the chosen subframes' sizes in bits, int32 [n_frames, channels].
+    lpc_order 1..8 adds LPC subframes up to that order to the search (0: FIXED only)."""
     import torch
+    lpc_order = _lpc_order(lpc_order)
     x = d_pcm16
     if x.dtype != torch.int16 or not x.is_cuda:
         raise ValueError("encode_flac_device takes an int16 tensor on the device")
@@ -146,8 +155,8 @@ def encode_flac_device(d_pcm16, fs, block=4096, sub_bits=False):
     frames, channels = int(x.shape[0]), int(x.shape[1])
     L = capi.load()
     nf, cap, wsb = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
-    capi.check(L.amx_flac_encode_size(frames, channels, int(block), ctypes.byref(nf), ctypes.byref(cap),
-                                      ctypes.byref(wsb)), "amx_flac_encode_size")
+    capi.check(L.amx_flac_encode_size_ex(frames, channels, int(block), lpc_order, ctypes.byref(nf),
+                                         ctypes.byref(cap), ctypes.byref(wsb)), "amx_flac_encode_size_ex")
     dev = x.device
     out = torch.empty(cap.value, dtype=torch.uint8, device=dev)
     fbytes = torch.empty(nf.value, dtype=torch.int32, device=dev)
@@ -155,19 +164,21 @@ def encode_flac_device(d_pcm16, fs, block=4096, sub_bits=False):
     total = torch.empty(1, dtype=torch.int64, device=dev)
     ws = torch.empty((wsb.value + 7) // 8, dtype=torch.int64, device=dev)
     with torch.cuda.device(dev):
-        capi.check(L.amx_flac_encode(capi.ptr(x), frames, channels, int(fs), int(block), capi.ptr(out), cap.value,
-                                     capi.ptr(fbytes), capi.ptr(sb), capi.ptr(total), capi.ptr(ws), ws.numel() * 8,
-                                     capi.ptr_stream()), "amx_flac_encode")
+        capi.check(L.amx_flac_encode_ex(capi.ptr(x), frames, channels, int(fs), int(block), lpc_order,
+                                        capi.ptr(out), cap.value, capi.ptr(fbytes), capi.ptr(sb), capi.ptr(total),
+                                        capi.ptr(ws), ws.numel() * 8, capi.ptr_stream()), "amx_flac_encode_ex")
         n = int(total.item())
     if sub_bits:
         return out[:n], fbytes, sb
     return out[:n], fbytes
 
 
-def flac_bytes(x16, fs, block=4096, md5=True):
-    """The FLAC file of int16 samples [frames, channels] (a device tensor or a numpy array)."""
+def flac_bytes(x16, fs, block=4096, md5=True, lpc_order=0):
+    """The FLAC file of int16 samples [frames, channels] (a device tensor or a numpy array);
+    lpc_order as in encode_flac_device."""
     import hashlib
     import torch
+    lpc_order = _lpc_order(lpc_order)
     if isinstance(x16, np.ndarray):
         x16 = torch.from_numpy(np.ascontiguousarray(x16, np.int16))
     if x16.dim() == 1:
@@ -180,13 +191,15 @@ def flac_bytes(x16, fs, block=4096, md5=True):
     if md5:
         # the host hashes the raw PCM: the D2H of the samples the encoder otherwise saves
         digest = hashlib.md5(x16.cpu().contiguous().numpy().astype("<i2", copy=False).tobytes()).digest()
-    payload, fbytes = encode_flac_device(x16.to("cuda"), fs, block)
+    payload, fbytes = encode_flac_device(x16.to("cuda"), fs, block, lpc_order=lpc_order)
     return flac_container(payload.cpu().numpy().tobytes(), fbytes.cpu().numpy(), fs, channels, frames, block, digest)
 
 
-def write_flac(path, x16, fs, block=4096, md5=True):
+def write_flac(path, x16, fs, block=4096, md5=True, lpc_order=0):
     """x16 int16 [frames, channels] (device tensor or numpy array) as a 16-bit FLAC file.
-    md5=False leaves STREAMINFO's MD5 zero and moves only the encoded bytes off the device."""
-    data = flac_bytes(x16, fs, block, md5)
+    md5=False leaves STREAMINFO's MD5 zero and moves only the encoded bytes off the device.
+    lpc_order 1..8: LPC subframes up to that order (a smaller file, one more kernel); an
+    order outside 0..8 raises ValueError and leaves no file."""
+    data = flac_bytes(x16, fs, block, md5, lpc_order)
     with open(path, "wb") as f:
         f.write(data)

@@ -7,7 +7,8 @@ Mirrors audio_mastering_engine.py's call surface for the hot path:
   ``settings`` keys and defaults, same status strings and progress sequence
   (``(0,100)``, ``(i+1, n+4)`` per chunk, ``n+1``, ``n+2`` only with ``lufs``,
   ``n+3``, ``n+4``), same ``ValueError`` for missing files, writes a 16-bit WAV -- or,
-  for an ``output_file`` named ``*.flac``, a 16-bit FLAC file encoded on the device.
+  for an ``output_file`` named ``*.flac``, a 16-bit FLAC file encoded on the device
+  (optional key ``flac_lpc_order`` 0..8: LPC subframes up to that order; absent: 0).
 * ``process_audio_with_ffmpeg_pipeline`` -- alias of ``master_audio``.
 * ``process_audio(settings, status_cb, progress_cb, art_cb, tag_cb)`` -- the GUI
   wrapper (:94-137): mastering, the optional MP3 export (:97-98, ``export_to_mp3``
@@ -79,14 +80,15 @@ def _device_input(path):
     return d_in, info.sample_rate, frames, 2, True, info
 
 
-def _write_output(path, y_device, fs):
+def _write_output(path, y_device, fs, settings=None):
     """The mastered int16 track (a device tensor) as the file ffmpeg's last command writes
     (:223, `-y output_file`: the extension picks the container): *.flac in any letter case
     is encoded on the device (amx.flacio.write_flac, with STREAMINFO's MD5); every other
-    name gets the 16-bit WAV."""
+    name gets the 16-bit WAV.  The optional settings key flac_lpc_order (0..8, absent: 0,
+    the FIXED-only file) is write_flac's lpc_order; a name that is not *.flac ignores it."""
     if os.path.splitext(str(path))[1].lower() == ".flac":
         from amx import flacio
-        flacio.write_flac(path, y_device, fs)
+        flacio.write_flac(path, y_device, fs, lpc_order=(settings or {}).get("flac_lpc_order", 0))
     else:
         wavio.write_wav_s16(path, y_device.cpu().numpy(), fs)
 
@@ -170,7 +172,7 @@ def master_audio(settings, status_callback=None, progress_callback=None):
     else:
         # the alimiter ran on the 192 kHz file inside dynamic_track (:223 keeps its rate)
         y, out_fs = dyn[0], dyn[1]["sample_rate"]
-    _write_output(output_file, y, out_fs)
+    _write_output(output_file, y, out_fs, settings)
     progress(total_steps, total_steps)                                        # :224
     logging.info(f"Finished GPU pipeline, exported to {output_file}")
     return output_file
@@ -206,7 +208,7 @@ def _master_multichannel(settings, status, progress, d_in, fs, frames, channels,
         job.measure(lufs_on=False)
     status("Applying final limiting and exporting...")                        # :221
     progress(num_chunks + 3, total_steps)                                     # :222
-    _write_output(output_file, job.finalize(), fs)
+    _write_output(output_file, job.finalize(), fs, settings)
     progress(total_steps, total_steps)                                        # :224
     logging.info(f"Finished GPU pipeline, exported to {output_file}")
     job.close()

@@ -8,11 +8,17 @@
 //   CONSTANT (all samples equal), VERBATIM, FIXED order 0..min(4, block);
 //   residual coding method 0 (4-bit Rice parameters), k 0..14, no escapes, partition
 //   order p 0..min(6, ctz(block)) with (block >> p) >= order;
-//   stereo: the smallest of independent, left/side, side/right, mid/side.
-// Three kernels (RFC 9639 for the bitstream):
+//   stereo: the smallest of independent, left/side, side/right, mid/side;
+//   with lpc_order M > 0 also LPC of order 1..min(M, block - 1): 12-bit coefficients from
+//   an integer Welch window, an exact integer autocorrelation and Levinson in fp64 in a
+//   fixed operation order (DESIGN.md §3.10 "LPC"), every folded residual below 2^22.
+// The kernels (RFC 9639 for the bitstream):
 //   k_flac_analyze  one workgroup per (frame, channel candidate): the exact minimum over
 //                   the search space and the choice that reaches it (one pass over the
 //                   samples, then one wave per predictor order)
+//   k_flac_lpc      (lpc_order > 0 only) one workgroup per (frame, channel candidate): the
+//                   LPC orders' exact sizes; the best replaces the analysis' choice when
+//                   it is strictly smaller
 //   k_flac_place    one workgroup: the channel assignment, each frame's byte length and
 //                   the exclusive scan of the lengths (the frames' offsets)
 //   k_flac_pack     one workgroup per frame: the frame staged in pre-zeroed LDS (codes
@@ -28,6 +34,8 @@ namespace amx {
 #define FE_MAXP 64           // finest partitions (partition order 6)
 #define FE_NK 15             // Rice parameters 0..14
 #define FE_CAP 0x3fffffffu   // sums saturate here: far above any VERBATIM size, never the minimum
+#define FE_MAXO 8            // LPC orders 1..8
+#define FE_LPC0 32           // cinfo / subframe type of LPC order o: FE_LPC0 + o - 1
 
 // workspace layout (amx_flac_encode_size): offsets i64 [nf], assign u32 [nf],
 // cbits u32 [nf][ncand], cinfo u32 [nf][ncand], ck u8 [nf][ncand][64]
@@ -35,6 +43,13 @@ struct FeWs {
     int64_t *off;
     uint32_t *assign, *cbits, *cinfo;
     uint8_t *ck;
+};
+// appended with lpc_order > 0: lq i16 [nf][ncand][8] (the coefficients), lsh u32 [nf][ncand]
+// (the shift), read only for the slots whose cinfo names an LPC subframe.  A structure of
+// its own: the lpc_order == 0 kernels keep their arguments.
+struct FeLpcWs {
+    int16_t *lq;
+    uint32_t *lsh;
 };
 __host__ __device__ static inline FeWs fe_ws(void *ws, int64_t nf, int ncand) {
     FeWs w;
@@ -50,6 +65,14 @@ __host__ __device__ static inline FeWs fe_ws(void *ws, int64_t nf, int ncand) {
     w.ck = p;
     return w;
 }
+__host__ __device__ static inline FeLpcWs fe_lpc_ws(const FeWs &ws, int64_t nf, int ncand) {
+    FeLpcWs w;
+    uint8_t *p = ws.ck + nf * ncand * FE_MAXP;
+    w.lq = reinterpret_cast<int16_t *>(p);
+    p += nf * ncand * FE_MAXO * 2;
+    w.lsh = reinterpret_cast<uint32_t *>(p);
+    return w;
+}
 
 // the sample of channel candidate `cand` at frame i: the file's channel, or for stereo
 // 0 L, 1 R, 2 mid = (L + R) >> 1, 3 side = L - R (17 bits)
@@ -59,6 +82,15 @@ __device__ __forceinline__ int fe_sample(const int16_t *__restrict__ pcm, int64_
     return cand == 0 ? l : cand == 1 ? r : cand == 2 ? ((l + r) >> 1) : (l - r);
 }
 
+// LPC residual of order o at i >= o: coefficients q[0 .. 8) (q[0] multiplies the sample just
+// before), shift sh.  Coefficients (12 bits) and samples (17) fit the 24-bit multiply.
+__device__ __forceinline__ int fe_lpc_residual(const int *s, int i, int o, const int *q, int sh) {
+    int acc = 0;
+#pragma unroll
+    for (int j = 0; j < FE_MAXO; j++)
+        if (j < o) acc += __mul24(q[j], s[i - 1 - j]);
+    return s[i] - (acc >> sh);
+}
 // FIXED predictor residual of order o at i >= o
 __device__ __forceinline__ int fe_residual(const int *s, int i, int o) {
     switch (o) {
@@ -84,6 +116,49 @@ __device__ __forceinline__ uint32_t fe_fold(int r) { return ((uint32_t)r << 1) ^
 // 2^22 bits, more than any VERBATIM subframe, so it is never part of the minimum and every
 // sum that can be is exact.
 #define FE_TCAP (1u << 22)
+
+// Phase 2 for one predictor order o, run by one whole wave: Srow holds the 2^pmax finest
+// partitions' fifteen sums, head the subframe's bits before the partitions' codes.  The
+// smallest size over the partition orders goes to best[0], its partition order to best[1]
+// and its Rice parameters to kout.
+__device__ __forceinline__ void fe_partition_search(const uint32_t *Srow, int lane, int n, int pmax, int o,
+                                                    uint32_t head, uint8_t *kout, uint32_t *best) {
+    const int P = 1 << pmax;
+    uint32_t S[FE_NK];
+#pragma unroll
+    for (int k = 0; k < FE_NK; k++) S[k] = lane < P ? Srow[lane * FE_NK + k] : 0u;
+    uint32_t btot = 0xffffffffu, bk = 0;
+    int bp = 0;
+    for (int p = pmax; p >= 0; p--) {
+        const int stride = 1 << (pmax - p), np = n >> p;
+        const bool active = lane < P && (lane & (stride - 1)) == 0;
+        const uint32_t nj = (uint32_t)(np - (lane == 0 ? o : 0));   // (np < o: the order is skipped)
+        uint32_t m = 0xffffffffu, mk = 0;
+#pragma unroll
+        for (int k = 0; k < FE_NK; k++) {
+            const uint32_t c = nj * (uint32_t)(k + 1) + S[k];
+            if (c < m) { m = c; mk = k; }
+        }
+        uint32_t c = active && np >= o ? 4u + m : 0u;
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint32_t x = c + __shfl_xor(c, d);
+            c = x < 0x7fffffffu ? x : 0x7fffffffu;
+        }
+        const uint32_t tot = head + c;
+        if (np >= o && tot < btot) { btot = tot; bp = p; bk = mk; }
+        if (p > 0) {
+#pragma unroll
+            for (int k = 0; k < FE_NK; k++) {
+                const uint32_t x = S[k] + __shfl_down(S[k], (unsigned)stride);
+                S[k] = x < FE_CAP ? x : FE_CAP;
+            }
+        }
+    }
+    const int sb = 1 << (pmax - bp);
+    if (lane < P && (lane & (sb - 1)) == 0) kout[lane >> (pmax - bp)] = (uint8_t)bk;
+    if (lane == 0) { best[0] = btot; best[1] = (uint32_t)bp; }
+}
+
 __global__ void __launch_bounds__(FE_NT) k_flac_analyze(const int16_t *__restrict__ pcm, int64_t frames, int C,
                                                         int B, int ncand, FeWs ws) {
     __shared__ int s[4608];
@@ -144,39 +219,7 @@ __global__ void __launch_bounds__(FE_NT) k_flac_analyze(const int16_t *__restric
 
     const int lane = t & 63;
     for (int o = t >> 6; o <= omax; o += FE_NT / 64) {
-        uint32_t S[FE_NK];
-#pragma unroll
-        for (int k = 0; k < FE_NK; k++) S[k] = lane < P ? Sall[o][lane * FE_NK + k] : 0u;
-        uint32_t btot = 0xffffffffu, bk = 0;
-        int bp = 0;
-        for (int p = pmax; p >= 0; p--) {
-            const int stride = 1 << (pmax - p), np = n >> p;
-            const bool active = lane < P && (lane & (stride - 1)) == 0;
-            const uint32_t nj = (uint32_t)(np - (lane == 0 ? o : 0));   // (np < o: the order is skipped)
-            uint32_t m = 0xffffffffu, mk = 0;
-#pragma unroll
-            for (int k = 0; k < FE_NK; k++) {
-                const uint32_t c = nj * (uint32_t)(k + 1) + S[k];
-                if (c < m) { m = c; mk = k; }
-            }
-            uint32_t c = active && np >= o ? 4u + m : 0u;
-            for (int d = 1; d < 64; d <<= 1) {
-                const uint32_t x = c + __shfl_xor(c, d);
-                c = x < 0x7fffffffu ? x : 0x7fffffffu;
-            }
-            const uint32_t tot = 8u + (uint32_t)(o * w) + 6u + c;
-            if (np >= o && tot < btot) { btot = tot; bp = p; bk = mk; }
-            if (p > 0) {
-#pragma unroll
-                for (int k = 0; k < FE_NK; k++) {
-                    const uint32_t x = S[k] + __shfl_down(S[k], (unsigned)stride);
-                    S[k] = x < FE_CAP ? x : FE_CAP;
-                }
-            }
-        }
-        const int sb = 1 << (pmax - bp);
-        if (lane < P && (lane & (sb - 1)) == 0) ordk[o][lane >> (pmax - bp)] = (uint8_t)bk;
-        if (lane == 0) { obest[o][0] = btot; obest[o][1] = (uint32_t)bp; }
+        fe_partition_search(Sall[o], lane, n, pmax, o, 8u + (uint32_t)(o * w) + 6u, ordk[o], obest[o]);
     }
     __syncthreads();
 
@@ -192,6 +235,222 @@ __global__ void __launch_bounds__(FE_NT) k_flac_analyze(const int16_t *__restric
         ws.cinfo[slot] = info;
     }
     if (t < FE_MAXP) ws.ck[slot * FE_MAXP + t] = bo >= 0 && t < (1 << bp) ? ordk[bo][t] : (uint8_t)0;
+}
+
+// ------------------------------------------------------------------ LPC
+// One workgroup per (frame, candidate), after k_flac_analyze.  The predictor of every order
+// is derived exactly as DESIGN.md §3.10 "LPC" fixes it, so that a host model recomputes the
+// same integers: an integer Welch window, the autocorrelation in exact int64 sums (any
+// order of adding gives the same R), Levinson and the quantisation in fp64 with every
+// operation a correctly rounded +, -, *, / (the build has -ffp-contract=off), run by wave 0,
+// every lane alike.  Then k_flac_analyze's phases 1 and 2, four orders at a time: the residuals'
+// sum(u >> k) per finest partition, one wave per order for the partition search.  An order
+// with a folded residual of FE_TCAP or more is no candidate.  The smallest candidate
+// replaces the slot's choice only when it is strictly below it; nothing is written
+// otherwise, and every word k_flac_pack reads of lq / lsh was written here.
+#define FE_LB 4              // orders per batch: 4 x 15 accumulators in registers
+// Phase 1 of k_flac_lpc for the orders ob + 1 .. ob + FE_LB: this lane's
+// samples of its finest partition, the orders' residuals, sum(u >> k) in registers, added
+// up over the partition's lanes into Sall.  An order that is no candidate adds zeros.
+__device__ __forceinline__ void fe_lpc_sums(const int *s, uint32_t *Sall, const int (*qs)[FE_MAXO], const int *shs,
+                                            const int *cand_ok, int *toobig, int ob, int Mp, int t, int plen,
+                                            int tpp) {
+    int cq[FE_LB][FE_MAXO], csh[FE_LB];
+    bool cok[FE_LB];
+#pragma unroll
+    for (int a = 0; a < FE_LB; a++) {
+        cok[a] = ob + a < Mp && cand_ok[ob + a];
+        csh[a] = cok[a] ? shs[ob + a] : 0;
+#pragma unroll
+        for (int j = 0; j < FE_MAXO; j++) cq[a][j] = cok[a] ? qs[ob + a][j] : 0;
+    }
+    uint32_t acc[FE_LB][FE_NK], umax[FE_LB];
+#pragma unroll
+    for (int a = 0; a < FE_LB; a++) {
+        umax[a] = 0;
+#pragma unroll
+        for (int k = 0; k < FE_NK; k++) acc[a][k] = 0;
+    }
+    // (each partition's lanes start rot samples in and wrap: with every partition starting at
+    // its first sample, a wave's reads lie a partition length apart, 64 words in a block of 4096)
+    const int j = t / tpp, q = t - j * tpp, rot = (j * tpp) % plen;
+    for (int m = q; m < plen; m += tpp) {
+        const int i = j * plen + (m + rot < plen ? m + rot : m + rot - plen);
+        int x[FE_MAXO + 1];
+#pragma unroll
+        for (int d = 0; d <= FE_MAXO; d++) x[d] = s[max(i - d, 0)];
+#pragma unroll
+        for (int a = 0; a < FE_LB; a++) {
+            // (taps beyond the order have coefficient 0; |sum| <= 8 * 2048 * 65535 < 2^30)
+            int sum = 0;
+#pragma unroll
+            for (int d = 0; d < FE_MAXO; d++) sum += __mul24(cq[a][d], x[d + 1]);
+            const uint32_t u = cok[a] && i >= ob + a + 1 ? fe_fold(x[0] - (sum >> csh[a])) : 0u;
+            umax[a] = u > umax[a] ? u : umax[a];
+#pragma unroll
+            for (int k = 0; k < FE_NK; k++) acc[a][k] += u >> k;
+        }
+    }
+    const int width = tpp < 64 ? tpp : 64;
+#pragma unroll
+    for (int a = 0; a < FE_LB; a++) {
+        if (umax[a] >= FE_TCAP) toobig[ob + a] = 1;
+#pragma unroll
+        for (int k = 0; k < FE_NK; k++) {
+            uint32_t v = acc[a][k] < FE_TCAP ? acc[a][k] : FE_TCAP;
+            for (int d = 1; d < width; d <<= 1) v += __shfl_xor(v, d);
+            if ((t & (width - 1)) == 0) atomicAdd(&Sall[a * FE_MAXP * FE_NK + j * FE_NK + k], v);
+        }
+    }
+}
+
+__global__ void __launch_bounds__(FE_NT) k_flac_lpc(const int16_t *__restrict__ pcm, int64_t frames, int C, int B,
+                                                    int ncand, int M, FeWs ws, FeLpcWs lw) {
+    __shared__ int s[4608];
+    __shared__ int buf[4608];                       // the windowed samples, then the batch's sums
+    __shared__ long long Rw[FE_NT / 64][FE_MAXO + 1];
+    __shared__ int qs[FE_MAXO][FE_MAXO];
+    __shared__ int shs[FE_MAXO], cand_ok[FE_MAXO], toobig[FE_MAXO];
+    __shared__ uint32_t obest[FE_MAXO][2];
+    __shared__ uint8_t ordk[FE_MAXO][FE_MAXP];
+    int *xw = buf;
+    uint32_t *Sall = reinterpret_cast<uint32_t *>(buf);   // [FE_LB][FE_MAXP * FE_NK]
+
+    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    const int64_t slot = (int64_t)blockIdx.x;
+    const int64_t f = slot / ncand;
+    const int cand = (int)(slot - f * ncand);
+    const int64_t i0 = f * B;
+    const int n = (int)(frames - i0 < B ? frames - i0 : B);
+    const int w = (C == 2 && cand == 3) ? 17 : 16;
+    const int Mp = M < n - 1 ? M : n - 1;
+    const uint32_t current = ws.cbits[slot];        // (read before anything here writes it)
+    if (Mp < 1) return;
+
+    if (t < FE_MAXO) { cand_ok[t] = 0; toobig[t] = 0; obest[t][0] = 0xffffffffu; obest[t][1] = 0; }
+    // W[i] = 1020 (i + 1) (n - i) / (n + 1)^2, floored.  Numerator (< 2^33) and denominator
+    // (< 2^25) are exact doubles and a quotient that is no integer lies at least 2^-25 from
+    // one, far more than the correctly rounded division's error: the floor is the integer's.
+    const double den = (double)((n + 1) * (n + 1));
+    for (int i = t; i < n; i += FE_NT) {
+        const int x = fe_sample(pcm, i0 + i, C, cand);
+        const int win = (int)(1020.0 * (double)((i + 1) * (n - i)) / den);
+        s[i] = x;
+        xw[i] = x * win;                            // |x| <= 65535, win <= 255: below 2^24
+    }
+    __syncthreads();
+
+    // R[l] = sum xw[i] xw[i - l]: products below 2^48, at most 4608 of them
+    long long R[FE_MAXO + 1];
+#pragma unroll
+    for (int l = 0; l <= FE_MAXO; l++) R[l] = 0;
+    for (int i = t; i < n; i += FE_NT) {
+        const long long a = xw[i];
+#pragma unroll
+        for (int l = 0; l <= FE_MAXO; l++)
+            if (l <= Mp && i >= l) R[l] += a * (long long)xw[i - l];
+    }
+#pragma unroll
+    for (int l = 0; l <= FE_MAXO; l++) {
+        long long v = R[l];
+        for (int d = 1; d < 64; d <<= 1) v += __shfl_xor(v, d);
+        if (lane == 0) Rw[wv][l] = v;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int l = 0; l <= FE_MAXO; l++) R[l] = Rw[0][l] + Rw[1][l] + Rw[2][l] + Rw[3][l];
+    if (R[0] == 0) return;                          // (the same R in every lane)
+
+    // Levinson and the quantisation of every order: wave 0 alone (the other waves' SIMDs are
+    // free for other workgroups meanwhile), the same in each of its lanes; lane 0 stores
+    if (wv == 0) {
+        double Rf[FE_MAXO + 1], lpc[FE_MAXO], nw[FE_MAXO];
+#pragma unroll
+        for (int l = 0; l <= FE_MAXO; l++) Rf[l] = (double)R[l];
+#pragma unroll
+        for (int j = 0; j < FE_MAXO; j++) lpc[j] = 0.0;
+        double err = Rf[0];
+        bool alive = true;
+#pragma unroll
+        for (int i = 0; i < FE_MAXO; i++) {
+            if (i < Mp && alive) {
+                double acc = Rf[i + 1];
+#pragma unroll
+                for (int j = 0; j < i; j++) acc = acc - lpc[j] * Rf[i - j];
+                const double k = acc / err;
+#pragma unroll
+                for (int j = 0; j < i; j++) nw[j] = lpc[j] - k * lpc[i - 1 - j];
+                nw[i] = k;
+#pragma unroll
+                for (int j = 0; j <= i; j++) lpc[j] = nw[j];
+                err = err * (1.0 - k * k);
+                if (!(err > 0.0)) alive = false;    // this order still counts, higher ones do not
+
+                // 12-bit coefficients: the largest shift that keeps them within 2047, error feedback
+                bool ok = true;
+                double cmax = 0.0;
+#pragma unroll
+                for (int j = 0; j <= i; j++) {
+                    const double a = fabs(lpc[j]);
+                    if (!(a <= 2047.0)) ok = false;
+                    if (a > cmax) cmax = a;
+                }
+                if (cmax == 0.0) ok = false;
+                int sh = -1;
+                for (int e = 15; e >= 0; e--)
+                    if (sh < 0 && cmax * (double)(1 << e) <= 2047.0) sh = e;
+                if (sh < 0) ok = false;
+                if (ok) {
+                    const double scale = (double)(1 << sh);
+                    double e = 0.0;
+#pragma unroll
+                    for (int j = 0; j <= i; j++) {
+                        e = e + lpc[j] * scale;
+                        int q = (int)floor(e + 0.5);
+                        q = q < -2048 ? -2048 : q > 2047 ? 2047 : q;
+                        e = e - (double)q;
+                        if (t == 0) qs[i][j] = q;
+                    }
+                    if (t == 0) {
+#pragma unroll
+                        for (int j = i + 1; j < FE_MAXO; j++) qs[i][j] = 0;
+                        shs[i] = sh;
+                        cand_ok[i] = 1;
+                    }
+                }
+            }
+        }
+    }
+
+    const int pmax = min(6, __ffs(n) - 1);
+    const int P = 1 << pmax, plen = n >> pmax, tpp = FE_NT / P;
+    for (int ob = 0; ob < Mp; ob += FE_LB) {
+        __syncthreads();                            // xw / the last batch's sums are done with; qs is there
+        for (int i = t; i < FE_LB * FE_MAXP * FE_NK; i += FE_NT) Sall[i] = 0;
+        __syncthreads();
+        fe_lpc_sums(s, Sall, qs, shs, cand_ok, toobig, ob, Mp, t, plen, tpp);
+        __syncthreads();
+        const int o = ob + wv + 1;                  // one wave per order of the batch
+        if (o <= Mp && cand_ok[o - 1] && !toobig[o - 1])
+            fe_partition_search(Sall + wv * FE_MAXP * FE_NK, lane, n, pmax, o,
+                                8u + (uint32_t)(o * w) + 4u + 5u + 12u * (uint32_t)o + 6u, ordk[o - 1],
+                                obest[o - 1]);
+    }
+    __syncthreads();
+
+    uint32_t best = current;
+    int bo = 0;
+    for (int o = 1; o <= Mp; o++)
+        if (cand_ok[o - 1] && !toobig[o - 1] && obest[o - 1][0] < best) { best = obest[o - 1][0]; bo = o; }
+    if (bo == 0) return;
+    const int bp = (int)obest[bo - 1][1];
+    if (t == 0) {
+        ws.cbits[slot] = best;
+        ws.cinfo[slot] = (uint32_t)(FE_LPC0 + bo - 1) | ((uint32_t)bp << 8);
+        lw.lsh[slot] = (uint32_t)shs[bo - 1];
+    }
+    if (t < FE_MAXO) lw.lq[slot * FE_MAXO + t] = (int16_t)qs[bo - 1][t];
+    if (t < FE_MAXP) ws.ck[slot * FE_MAXP + t] = t < (1 << bp) ? ordk[bo - 1][t] : (uint8_t)0;
 }
 
 // ------------------------------------------------------------------ frame header
@@ -348,10 +607,13 @@ __device__ __forceinline__ uint32_t fe_gf16_mul(uint32_t a, uint32_t b) {
 }
 
 // dynamic LDS: W [wwords] | s [B] | scan [FE_NT] | crc table [256] | misc [4]
+// LPC false: the lpc_order == 0 encoder's kernel, with no LPC branch in it
+template <bool LPC>
 __global__ void __launch_bounds__(FE_NT) k_flac_pack(const int16_t *__restrict__ pcm, int64_t frames, int C, int B,
                                                      int fs, int ncand, FeWs ws,
                                                      const uint32_t *__restrict__ frame_bytes,
-                                                     uint8_t *__restrict__ out, int64_t capacity, int wwords) {
+                                                     uint8_t *__restrict__ out, int64_t capacity, int wwords,
+                                                     FeLpcWs lw) {
     extern __shared__ __attribute__((aligned(16))) uint32_t fe_lds[];
     uint32_t *W = fe_lds;
     int *s = reinterpret_cast<int *>(fe_lds + wwords);
@@ -401,10 +663,24 @@ __global__ void __launch_bounds__(FE_NT) k_flac_pack(const int16_t *__restrict__
             for (int i = t; i < n; i += FE_NT)
                 fe_put(W, (uint32_t)wwords, pos + 8 + (uint32_t)i * w, (uint32_t)s[i] & wmask, w);
         } else {
-            const int o = type - 8;
+            // FIXED, or LPC: after the warm-up samples the precision (12 bits: 0b1011), the
+            // 5-bit shift and o 12-bit coefficients, then the residual as for FIXED
+            const bool lpc = LPC && type >= FE_LPC0;
+            const int o = lpc ? type - FE_LPC0 + 1 : type - 8;
             const uint8_t *kk = ws.ck + slot * FE_MAXP;
+            int qv[FE_MAXO], lsh = 0;
+#pragma unroll
+            for (int j = 0; j < FE_MAXO; j++) qv[j] = 0;
+            if (lpc) {
+                lsh = (int)lw.lsh[slot];
+#pragma unroll
+                for (int j = 0; j < FE_MAXO; j++) qv[j] = lw.lq[slot * FE_MAXO + j];
+            }
             if (t < o) fe_put(W, (uint32_t)wwords, pos + 8 + (uint32_t)t * w, (uint32_t)s[t] & wmask, w);
-            const uint32_t base = pos + 8 + (uint32_t)o * w + 6;
+            const uint32_t coef = pos + 8 + (uint32_t)o * w;
+            if (lpc && t == 0) fe_put(W, (uint32_t)wwords, coef, (11u << 5) | (uint32_t)lsh, 9);
+            if (lpc && t < o) fe_put(W, (uint32_t)wwords, coef + 9 + 12u * t, (uint32_t)lw.lq[slot * FE_MAXO + t] & 0xfffu, 12);
+            const uint32_t base = coef + (lpc ? 9u + 12u * o : 0u) + 6;
             if (t == 0) {
                 fe_put(W, (uint32_t)wwords, base - 6, (uint32_t)p, 6);           // coding method 00, partition order
                 fe_put(W, (uint32_t)wwords, base, kk[0], 4);
@@ -416,7 +692,7 @@ __global__ void __launch_bounds__(FE_NT) k_flac_pack(const int16_t *__restrict__
             uint32_t mine = 0;
             for (int i = a; i < b; i++) {
                 const int k = kk[i / plen];
-                mine += (fe_fold(fe_residual(s, i, o)) >> k) + 1u + k;
+                mine += (fe_fold(LPC && lpc ? fe_lpc_residual(s, i, o, qv, lsh) : fe_residual(s, i, o)) >> k) + 1u + k;
             }
             scan[t] = mine;
             __syncthreads();
@@ -429,7 +705,7 @@ __global__ void __launch_bounds__(FE_NT) k_flac_pack(const int16_t *__restrict__
             uint32_t at = scan[t] - mine;
             for (int i = a; i < b; i++) {
                 const int j = i / plen, k = kk[j];
-                const uint32_t u = fe_fold(fe_residual(s, i, o));
+                const uint32_t u = fe_fold(LPC && lpc ? fe_lpc_residual(s, i, o, qv, lsh) : fe_residual(s, i, o));
                 const uint32_t q = u >> k;
                 const uint32_t cp = base + 4u * (j + 1) + at;   // after the j + 1 parameters before it
                 if (j > 0 && i == j * plen) fe_put(W, (uint32_t)wwords, cp - 4, (uint32_t)k, 4);
@@ -483,7 +759,8 @@ __global__ void __launch_bounds__(FE_NT) k_flac_pack(const int16_t *__restrict__
 // the largest frame in bytes: a 16-byte header, every subframe VERBATIM at 17 bits, CRC-16
 static int64_t fe_frame_bound(int C, int n) { return 16 + ((int64_t)C * (8 + 17 * (int64_t)n) + 7) / 8 + 2; }
 
-void flac_encode_size(int64_t frames, int C, int B, int64_t *nf, int64_t *max_out, int64_t *ws_bytes) {
+void flac_encode_size(int64_t frames, int C, int B, int lpc_order, int64_t *nf, int64_t *max_out,
+                      int64_t *ws_bytes) {
     const int64_t n = (frames + B - 1) / B;
     const int last = (int)(frames - (n - 1) * B);
     const int ncand = C == 2 ? 4 : C;
@@ -492,30 +769,41 @@ void flac_encode_size(int64_t frames, int C, int B, int64_t *nf, int64_t *max_ou
     // the slack only keeps the buffer's end aligned)
     *max_out = ((n - 1) * fe_frame_bound(C, B) + fe_frame_bound(C, last) + 3) / 4 * 4;
     *ws_bytes = n * 8 + n * 4 + 2 * n * ncand * 4 + n * ncand * FE_MAXP;
+    // (an LPC subframe is chosen only below VERBATIM: the frame bound stands)
+    if (lpc_order > 0) *ws_bytes += n * ncand * (FE_MAXO * 2 + 4);
 }
 
-hipError_t launch_flac_encode(const int16_t *pcm, int64_t frames, int C, int fs, int B, uint8_t *out,
+hipError_t launch_flac_encode(const int16_t *pcm, int64_t frames, int C, int fs, int B, int lpc_order, uint8_t *out,
                               int64_t capacity, uint32_t *frame_bytes, uint32_t *sub_bits, int64_t *total,
                               void *wsp, hipStream_t st) {
     const int64_t nf = (frames + B - 1) / B;
     const int ncand = C == 2 ? 4 : C;
     if (nf * ncand > 0x7fffffffLL) return hipErrorInvalidValue;
     const FeWs ws = fe_ws(wsp, nf, ncand);
+    const FeLpcWs lw = fe_lpc_ws(ws, nf, ncand);
     hipLaunchKernelGGL(k_flac_analyze, dim3((unsigned)(nf * ncand)), dim3(FE_NT), 0, st, pcm, frames, C, B, ncand,
                        ws);
+    if (lpc_order > 0)
+        hipLaunchKernelGGL(k_flac_lpc, dim3((unsigned)(nf * ncand)), dim3(FE_NT), 0, st, pcm, frames, C, B, ncand,
+                           lpc_order, ws, lw);
     hipLaunchKernelGGL(k_flac_place, dim3(1), dim3(FE_PL), 0, st, frames, C, B, fs, ncand, nf, ws, frame_bytes,
                        sub_bits, total);
     const int wwords = (int)((fe_frame_bound(C, (int)(frames < B ? frames : B)) + 3) / 4 + 1);
     const size_t lds = (size_t)(wwords + B + FE_NT + 256 + 4) * 4;
+    const void *pack = lpc_order > 0 ? reinterpret_cast<const void *>(k_flac_pack<true>)
+                                     : reinterpret_cast<const void *>(k_flac_pack<false>);
     if (lds > 64 * 1024) {
         // one workgroup may hold up to a CU's whole LDS (160 KiB on gfx950); the largest
         // request here (8 channels, block 4608) is 98 KiB
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_flac_pack),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        const hipError_t e = hipFuncSetAttribute(pack, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(k_flac_pack, dim3((unsigned)nf), dim3(FE_NT), lds, st, pcm, frames, C, B, fs, ncand, ws,
-                       frame_bytes, out, capacity, wwords);
+    if (lpc_order > 0)
+        hipLaunchKernelGGL(k_flac_pack<true>, dim3((unsigned)nf), dim3(FE_NT), lds, st, pcm, frames, C, B, fs,
+                           ncand, ws, frame_bytes, out, capacity, wwords, lw);
+    else
+        hipLaunchKernelGGL(k_flac_pack<false>, dim3((unsigned)nf), dim3(FE_NT), lds, st, pcm, frames, C, B, fs,
+                           ncand, ws, frame_bytes, out, capacity, wwords, lw);
     return hipGetLastError();
 }
 

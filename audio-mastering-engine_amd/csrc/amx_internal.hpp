@@ -95,9 +95,11 @@ hipError_t launch_mc_limiter_out(const int16_t *y, int64_t frames, int C, int ha
 hipError_t launch_zero(void *p, size_t bytes, hipStream_t st);   // a kernel, never a memset node
 hipError_t launch_pcm_to_s16(const void *raw, int64_t frames, int channels, int fmt, int16_t *out,
                              hipStream_t st);
-// FLAC output (amx_flacenc.hip): sizes for, and the three kernels of, amx_flac_encode
-void flac_encode_size(int64_t frames, int C, int B, int64_t *nf, int64_t *max_out, int64_t *ws_bytes);
-hipError_t launch_flac_encode(const int16_t *pcm, int64_t frames, int C, int fs, int B, uint8_t *out,
+// FLAC output (amx_flacenc.hip): sizes for, and the kernels of, amx_flac_encode_ex
+// (lpc_order 0: the FIXED-only search, three kernels and the workspace of amx_flac_encode)
+void flac_encode_size(int64_t frames, int C, int B, int lpc_order, int64_t *nf, int64_t *max_out,
+                      int64_t *ws_bytes);
+hipError_t launch_flac_encode(const int16_t *pcm, int64_t frames, int C, int fs, int B, int lpc_order, uint8_t *out,
                               int64_t capacity, uint32_t *frame_bytes, uint32_t *sub_bits, int64_t *total,
                               void *ws, hipStream_t st);
 hipError_t launch_env(const DynLaunch &d, const uint16_t *m, double *ck, double *sv, double *ev,

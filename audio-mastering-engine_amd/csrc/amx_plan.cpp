@@ -768,43 +768,57 @@ int amx_pcm_to_s16(const void *d_raw, int64_t frames, int32_t channels, int32_t 
     return AMX_OK;
 }
 
-static int flac_encode_args(int64_t frames, int32_t channels, int32_t block) {
+static int flac_encode_args(int64_t frames, int32_t channels, int32_t block, int32_t lpc_order) {
     if (channels < 1 || channels > 8) return fail(AMX_EINVAL, "channels must be 1..8");
     if (frames < 1) return fail(AMX_EINVAL, "frames must be >= 1");
     if (block < 16 || block > 4608) return fail(AMX_ERANGE, "block size %d outside 16..4608", block);
+    if (lpc_order < 0 || lpc_order > 8) return fail(AMX_ERANGE, "lpc_order %d outside 0..8", lpc_order);
+    return AMX_OK;
+}
+
+int amx_flac_encode_size_ex(int64_t frames, int32_t channels, int32_t block, int32_t lpc_order,
+                            int64_t *n_frames, int64_t *max_out_bytes, int64_t *workspace_bytes) {
+    if (!n_frames || !max_out_bytes || !workspace_bytes) return fail(AMX_EINVAL, "null argument");
+    const int rc = flac_encode_args(frames, channels, block, lpc_order);
+    if (rc != AMX_OK) return rc;
+    amx::flac_encode_size(frames, channels, block, lpc_order, n_frames, max_out_bytes, workspace_bytes);
     return AMX_OK;
 }
 
 int amx_flac_encode_size(int64_t frames, int32_t channels, int32_t block, int64_t *n_frames,
                          int64_t *max_out_bytes, int64_t *workspace_bytes) {
-    if (!n_frames || !max_out_bytes || !workspace_bytes) return fail(AMX_EINVAL, "null argument");
-    const int rc = flac_encode_args(frames, channels, block);
-    if (rc != AMX_OK) return rc;
-    amx::flac_encode_size(frames, channels, block, n_frames, max_out_bytes, workspace_bytes);
-    return AMX_OK;
+    return amx_flac_encode_size_ex(frames, channels, block, 0, n_frames, max_out_bytes, workspace_bytes);
 }
 
 int amx_flac_encode(const int16_t *d_pcm, int64_t frames, int32_t channels, int32_t sample_rate,
                     int32_t block, uint8_t *d_out, int64_t out_capacity, uint32_t *d_frame_bytes,
                     uint32_t *d_sub_bits, int64_t *d_total_bytes, void *workspace,
                     int64_t workspace_bytes, void *stream) {
+    return amx_flac_encode_ex(d_pcm, frames, channels, sample_rate, block, 0, d_out, out_capacity, d_frame_bytes,
+                              d_sub_bits, d_total_bytes, workspace, workspace_bytes, stream);
+}
+
+int amx_flac_encode_ex(const int16_t *d_pcm, int64_t frames, int32_t channels, int32_t sample_rate,
+                       int32_t block, int32_t lpc_order, uint8_t *d_out, int64_t out_capacity,
+                       uint32_t *d_frame_bytes, uint32_t *d_sub_bits, int64_t *d_total_bytes, void *workspace,
+                       int64_t workspace_bytes, void *stream) {
     if (!d_pcm || !d_out || !d_frame_bytes || !d_total_bytes || !workspace)
         return fail(AMX_EINVAL, "null argument");
-    const int rc = flac_encode_args(frames, channels, block);
+    const int rc = flac_encode_args(frames, channels, block, lpc_order);
     if (rc != AMX_OK) return rc;
     if (sample_rate < 1 || sample_rate > 1048575)
         return fail(AMX_ERANGE, "sample rate %d outside 1..1048575", sample_rate);
     if (reinterpret_cast<uintptr_t>(workspace) & 7) return fail(AMX_EINVAL, "workspace must be 8-byte aligned");
     int64_t nf, max_out, ws_bytes;
-    amx::flac_encode_size(frames, channels, block, &nf, &max_out, &ws_bytes);
+    amx::flac_encode_size(frames, channels, block, lpc_order, &nf, &max_out, &ws_bytes);
     if (out_capacity < max_out)
         return fail(AMX_ERANGE, "out_capacity %lld < %lld (amx_flac_encode_size)", (long long)out_capacity,
                     (long long)max_out);
     if (workspace_bytes < ws_bytes)
         return fail(AMX_ERANGE, "workspace_bytes %lld < %lld (amx_flac_encode_size)", (long long)workspace_bytes,
                     (long long)ws_bytes);
-    HIPCHK(amx::launch_flac_encode(d_pcm, frames, channels, sample_rate, block, d_out, out_capacity, d_frame_bytes,
-                                   d_sub_bits, d_total_bytes, workspace, (hipStream_t)stream));
+    HIPCHK(amx::launch_flac_encode(d_pcm, frames, channels, sample_rate, block, lpc_order, d_out, out_capacity,
+                                   d_frame_bytes, d_sub_bits, d_total_bytes, workspace, (hipStream_t)stream));
     return AMX_OK;
 }
 

@@ -48,8 +48,11 @@ extern "C" {
  * frames per track, amx_final_desc.pad_ became `from_rest`.  A caller built against
  * an older header must be rebuilt: amx_abi_version() tells it which layout it gets.
  * 4 -> 5: amx_flac_encode_size and amx_flac_encode added (the FLAC output); no layout
- * of an existing structure changed. */
-#define AMX_ABI_VERSION 5
+ * of an existing structure changed.
+ * 5 -> 6: amx_flac_encode_size_ex and amx_flac_encode_ex added (lpc_order: LPC subframes
+ * of order 1..8 in the FLAC output); the two older entry points are the _ex forms with
+ * lpc_order 0 and give the same sizes and bytes as before. */
+#define AMX_ABI_VERSION 6
 
 #if defined(__GNUC__)
 #define AMX_API __attribute__((visibility("default")))
@@ -271,6 +274,21 @@ AMX_API int amx_flac_encode(const int16_t *d_pcm, int64_t frames, int32_t channe
                             int32_t block, uint8_t *d_out, int64_t out_capacity, uint32_t *d_frame_bytes,
                             uint32_t *d_sub_bits, int64_t *d_total_bytes, void *workspace,
                             int64_t workspace_bytes, void *stream);
+
+/* (ABI 6) The same with lpc_order 0..8 (anything else: AMX_ERANGE, before any launch).
+ * lpc_order 0 is amx_flac_encode_size / amx_flac_encode: the same sizes, the same bytes.
+ * lpc_order M > 0 adds to every subframe's search space LPC of order 1..min(M, frame
+ * length - 1) with 12-bit coefficients (DESIGN.md 3.10 "LPC": integer Welch window, exact
+ * integer autocorrelation, Levinson and quantisation in fp64 in a fixed operation order,
+ * every folded residual below 2^22); the subframe is still the smallest of all candidates.
+ * One more kernel runs and the workspace grows by 20 bytes per (frame, channel candidate);
+ * the d_out capacity is the same. */
+AMX_API int amx_flac_encode_size_ex(int64_t frames, int32_t channels, int32_t block, int32_t lpc_order,
+                                    int64_t *n_frames, int64_t *max_out_bytes, int64_t *workspace_bytes);
+AMX_API int amx_flac_encode_ex(const int16_t *d_pcm, int64_t frames, int32_t channels, int32_t sample_rate,
+                               int32_t block, int32_t lpc_order, uint8_t *d_out, int64_t out_capacity,
+                               uint32_t *d_frame_bytes, uint32_t *d_sub_bits, int64_t *d_total_bytes,
+                               void *workspace, int64_t workspace_bytes, void *stream);
 
 /* Diagnostics of the compressor envelope's fix-up (AMX_STAGE_FIX) of the last step run
  * on d_ws: out[0..3] = segments the chain walkers re-ran, the longest walk (segments one

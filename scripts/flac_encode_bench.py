@@ -12,7 +12,12 @@ plus the compression ratio and, on the host clock, hashlib.md5 over the raw PCM 
 write_flac(md5=True) adds: it also needs the raw copy).  No pass mark: the numbers go to
 profiles/flac_encode_bench.json and DESIGN.md 3.10.
 
-    python scripts/flac_encode_bench.py [--seconds 300] [--reps 15] [--block 4096]
+--lpc-order takes one order or a comma-separated list (amx_flac_encode_ex; 0 is the
+FIXED-only encoder): "masters" holds the first order's numbers, "masters_lpcN" those of every
+further order N, measured on the same masters in the same process
+(profiles/flac_lpc_bench.json).
+
+    python scripts/flac_encode_bench.py [--seconds 300] [--reps 15] [--block 4096] [--lpc-order 0,4,8]
 """
 import argparse
 import ctypes
@@ -81,25 +86,26 @@ def timed(fn, reps, warmup=3):
     return {"median_ms": round(statistics.median(ms), 4), "min_ms": round(min(ms), 4), "max_ms": round(max(ms), 4)}
 
 
-def measure(y, rate, block, reps):
+def measure(y, rate, block, reps, lpc_order=0):
     import torch
     from amx import capi, flacio
     L = capi.load()
     frames, C = int(y.shape[0]), int(y.shape[1])
     nf, cap, wsb = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
-    capi.check(L.amx_flac_encode_size(frames, C, block, ctypes.byref(nf), ctypes.byref(cap), ctypes.byref(wsb)),
-               "amx_flac_encode_size")
+    capi.check(L.amx_flac_encode_size_ex(frames, C, block, lpc_order, ctypes.byref(nf), ctypes.byref(cap),
+                                         ctypes.byref(wsb)), "amx_flac_encode_size_ex")
     out = torch.empty(cap.value, dtype=torch.uint8, device="cuda")
     fb = torch.empty(nf.value, dtype=torch.int32, device="cuda")
     total = torch.empty(1, dtype=torch.int64, device="cuda")
     ws = torch.empty((wsb.value + 7) // 8, dtype=torch.int64, device="cuda")
 
     def encode():
-        capi.check(L.amx_flac_encode(capi.ptr(y), frames, C, rate, block, capi.ptr(out), cap.value, capi.ptr(fb),
-                                     None, capi.ptr(total), capi.ptr(ws), ws.numel() * 8, capi.ptr_stream()),
-                   "amx_flac_encode")
+        capi.check(L.amx_flac_encode_ex(capi.ptr(y), frames, C, rate, block, lpc_order, capi.ptr(out), cap.value,
+                                        capi.ptr(fb), None, capi.ptr(total), capi.ptr(ws), ws.numel() * 8,
+                                        capi.ptr_stream()), "amx_flac_encode_ex")
 
-    r = {"frames": frames, "channels": C, "sample_rate": rate, "block": block, "flac_frames": nf.value}
+    r = {"frames": frames, "channels": C, "sample_rate": rate, "block": block, "flac_frames": nf.value,
+         "lpc_order": lpc_order}
     r["encode"] = timed(encode, reps)
     n_enc = int(total.item())
     raw_bytes = frames * C * 2
@@ -134,6 +140,8 @@ def main():
     ap.add_argument("--seconds", type=float, default=300.0)
     ap.add_argument("--reps", type=int, default=15)
     ap.add_argument("--block", type=int, default=4096)
+    ap.add_argument("--lpc-order", default=[0], type=lambda s: [int(v) for v in s.split(",")],
+                    help="LPC order 0..8, or a comma-separated list of orders")
     ap.add_argument("--rev", default=None, help="the revision to record (default: git's HEAD)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "flac_encode_bench.json"))
     args = ap.parse_args()
@@ -143,7 +151,9 @@ def main():
            "git": args.rev or git_rev(), "device": torch.cuda.get_device_name(0), "seconds": args.seconds,
            "masters": {}}
     for name, (y, rate) in masters(args.seconds).items():
-        res["masters"][name] = measure(y, rate, args.block, args.reps)
+        for i, order in enumerate(args.lpc_order):
+            res.setdefault("masters" if i == 0 else "masters_lpc%d" % order, {})[name] = \
+                measure(y, rate, args.block, args.reps, order)
     line = json.dumps(res)
     print(line)
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
