@@ -142,7 +142,50 @@ def cases(ame):
     out.append(("mc4_mb_only_96k", 96000, 4800, 4, "music", dict(**MB)))
     out.append(("mc5_neg_shelf_48k", 48000, 3001, 5, "music", dict(bass_boost=-3.0, treble_boost=-2.0)))
     out.append(("mc8_pass_48k", 48000, 2000, 8, "music", dict()))
+    # every EQ stage combination (mask bit 0 bass, 1 mid, 2 presence, 3 treble) and shelf
+    # sign: with the cases above the stereo fixtures hold all 36 (mask, shelf-sign) cases,
+    # the mc fixtures all 16 masks.  EQ only, 2600 + 37 i frames (two scan blocks of 16
+    # segments of 128 and a ragged last segment).  APPENDED: the seed is the list index.
+    for i, (mask, sb, st) in enumerate(EQ_STEREO_NEW):
+        fs = (44100, 48000, 96000)[i % 3]
+        out.append(("eq_m%02d_b%s_t%s" % (mask, "0pn"[sb], "0pn"[st]), fs, 2600 + 37 * i, 2,
+                    "music", eq_settings(mask, sb, st)))
+    # 3 / 4 channels, one per mask; each shelf takes each sign with and without peak
+    # stages beside it; multiband on for two cases of every four, so that it meets both
+    # channel counts
+    for i in range(16):
+        fs = (44100, 48000, 96000)[i % 3]
+        sb, st = MC_BASS_SIGN[i >> 1] if i & 1 else 0, MC_TREBLE_SIGN[i - 8] if i & 8 else 0
+        s = eq_settings(i, sb, st)
+        mb = i % 4 in (1, 2)
+        if mb:
+            s.update(MB)
+        # (under 100 KB each: a multiband fixture stores six band arrays more, and four
+        # channels are a third more samples, so those are shorter)
+        out.append(("mc%d_eq_m%02d_b%s_t%s" % (3 + i % 2, i, "0pn"[sb], "0pn"[st]), fs,
+                    (500 if mb else 900 if i % 2 else 1200) + 37 * i, 3 + i % 2, "music", s))
     return out
+
+
+EQ_GAIN = dict(bass_boost=3.0, mid_cut=4.0, presence_boost=2.5, treble_boost=2.0)
+# (mask, bass sign, treble sign); sign 1 = +, 2 = -, 0 = stage off
+EQ_STEREO_NEW = [
+    (3, 1, 0), (3, 2, 0), (4, 0, 0), (5, 1, 0), (5, 2, 0), (6, 0, 0), (7, 1, 0), (7, 2, 0),
+    (10, 0, 1), (10, 0, 2), (11, 1, 1), (11, 1, 2), (11, 2, 1), (11, 2, 2), (14, 0, 1), (14, 0, 2),
+    (1, 2, 0), (8, 0, 1), (9, 1, 2), (9, 2, 1), (12, 0, 2), (13, 1, 1), (13, 2, 1), (13, 2, 2),
+    (15, 1, 2)]
+MC_BASS_SIGN = (1, 2, 1, 2, 2, 1, 2, 1)        # masks 1, 3, ..., 15
+MC_TREBLE_SIGN = (2, 1, 1, 2, 2, 1, 1, 2)      # masks 8 ... 15
+
+
+def eq_settings(mask, sb, st):
+    s = {k: EQ_GAIN[k] for b, k in enumerate(("bass_boost", "mid_cut", "presence_boost", "treble_boost"))
+         if mask >> b & 1}
+    if sb == 2:
+        s["bass_boost"] = -s["bass_boost"]
+    if st == 2:
+        s["treble_boost"] = -s["treble_boost"]
+    return s
 
 
 def make_signal(kind, n, fs, channels, seed):

@@ -21,7 +21,31 @@ FILES = [p for p in ALL_FILES if p not in MC_FILES]
 
 
 def test_golden_present():
-    assert len(FILES) >= 15
+    assert len(FILES) >= 44
+
+
+def _eq_case(settings):
+    """(mask, bass sign, treble sign) of a settings dict: mask bit 0 bass, 1 mid, 2 presence,
+    3 treble (the stages whose gain is not 0 -- oracle.eq_struct, amx_plan_build.cpp)"""
+    g = [settings.get(k) or 0.0 for k in ("bass_boost", "mid_cut", "presence_boost", "treble_boost")]
+    mask = sum(1 << b for b in range(4) if g[b] != 0)
+    return mask, int(np.sign(g[0])), int(np.sign(g[3]))
+
+
+def test_golden_cover_every_eq_mask_and_shelf_sign():
+    """The EQ mask picks the kernel instantiations (state dimension, coefficient offsets,
+    state slots) and a negative shelf takes another formula, whose first product is float32
+    only on the first active stage: the fixtures hold all 36 (mask, shelf-sign) cases in
+    stereo and all 16 masks at 3..8 channels, and pruning them must not reopen the gap"""
+    def seen(files):
+        return {_eq_case(json.loads(str(np.load(p)["meta"]))["settings"]) for p in files}
+    want = {(m, sb if m & 1 else 0, st if m & 8 else 0)
+            for m in range(16) for sb in (1, -1) for st in (1, -1)}
+    assert len(want) == 36
+    missing = want - seen(FILES)        # a mono fixture runs the stereo chain too (:190)
+    assert not missing, "stereo fixtures lack (mask, bass sign, treble sign) %s" % sorted(missing)
+    masks = {m for m, _, _ in seen(MC_FILES)}
+    assert masks == set(range(16)), "mc fixtures lack masks %s" % sorted(set(range(16)) - masks)
 
 
 @pytest.mark.parametrize("path", FILES, ids=lambda p: os.path.basename(p)[:-4])
@@ -74,7 +98,7 @@ def test_oracle_multichannel_matches_reference_golden(oracle_mod, path):
 
 
 def test_golden_multichannel_present():
-    assert len(MC_FILES) >= 6
+    assert len(MC_FILES) >= 22
 
 
 def test_audioop_known_answers(oracle_mod):
