@@ -444,8 +444,8 @@ class MasteringJob:
         complete step.  dynamic: the step also holds loudnorm's dynamic path
         (prepare_dynamic), so a track that takes it is finished inside the step too --
         enqueued by replay() after the graph, for the tracks whose published decision
-        word says dynamic (AMX_DYN_INLINE=1: gated inside the graph instead).
-        dyn_graph (default AMX_DYN_GRAPH, off): that path of each track is captured into
+        word says dynamic.
+        dyn_graph (default off): that path of each track is captured into
         a graph of its own as well, and replay() launches the track's graph instead of
         the ~35 eager launches.  (Round 5 measured such a graph 10-20x slower with walker
         re-runs: a captured hipMemsetAsync's fill node left the filter's boundary
@@ -454,13 +454,9 @@ class MasteringJob:
         profiles/r06c_dyn_graph_probe_zero_kernel.log.)"""
         self._dyn_eager = False
         self._dyn_graphs = None
-        if dyn_graph is None:
-            dyn_graph = os.environ.get("AMX_DYN_GRAPH") == "1"
         if dynamic:
             self.prepare_dynamic()
         dyn = bool(self._dyn_sides)
-        if os.environ.get("AMX_DYN_INLINE") == "1":
-            dyn = False      # (diagnostics: the gated dynamic path inside the step's graph)
         if dyn:
             # k_decide stores the decision words here as well (amx_plan_set_publish): the
             # host reads them while the limiter kernel still runs

@@ -13,13 +13,10 @@
 // coalesced dword traffic, recursion reads from LDS.
 #include "amx_dev.hpp"
 
-// AMX_VT_LATE (the segment kernels' tile movers: front1s_run, k_gemv16, vt_fetch): a
-// prefetched tile is masked when it is put into LDS, not right after its load -- a select
-// beside the load made the compiler wait for the prefetch at once -- and the prefetch is
-// unconditional (past the last tile it re-reads the current one)
-#ifndef AMX_VT_LATE
-#define AMX_VT_LATE 1
-#endif
+// The segment kernels' tile movers (front1s_run, k_gemv16, vt_fetch): a prefetched tile
+// is masked when it is put into LDS, not right after its load -- a select beside the load
+// made the compiler wait for the prefetch at once -- and the prefetch is unconditional
+// (past the last tile it re-reads the current one)
 
 namespace amx {
 
@@ -152,20 +149,12 @@ __device__ __forceinline__ void front1s_run(const ChainDev &cd, const float *__r
     uint4 R[4], RG;
     auto fetch = [&](int k) {
         const int tt = threadIdx.x;
-#if AMX_VT_LATE
         RG = *reinterpret_cast<const uint4 *>(G + (int64_t)k * D + 2 * (tt < GQ ? tt : 0));
-#else
-        RG = tt < GQ ? *reinterpret_cast<const uint4 *>(G + (int64_t)k * D + 2 * tt)
-                     : make_uint4(0u, 0u, 0u, 0u);
-#endif
 #pragma unroll
         for (int m = 0; m < 4; m++) {
             if constexpr (PART) {
                 const bool ok = k + 2 * c4 < ilen[m];          // frames k + 2 c4, +1
                 R[m] = *reinterpret_cast<const uint4 *>(ip[m] + (ok ? 2 * k : -4 * c4));
-#if !AMX_VT_LATE
-                if (!ok) R[m] = make_uint4(0u, 0u, 0u, 0u);
-#endif
             } else {
                 R[m] = *reinterpret_cast<const uint4 *>(ip[m] + 2 * k);
             }
@@ -177,22 +166,16 @@ __device__ __forceinline__ void front1s_run(const ChainDev &cd, const float *__r
 #pragma unroll
         for (int m = 0; m < 4; m++) {
             uint4 v = R[m];
-#if AMX_VT_LATE
-            if constexpr (PART) {                               // (AMX_VT_LATE: masked here)
+            if constexpr (PART) {                               // (masked here, not at the load)
                 if (!(k + 2 * c4 < ilen[m])) v = make_uint4(0u, 0u, 0u, 0u);
             }
-#endif
             uint32_t *w = s_in + (rg + 32 * m) * AMX_F1_PITCH + 4 * c4;
             *reinterpret_cast<uint2 *>(w) = make_uint2(v.x, v.y);
             *reinterpret_cast<uint2 *>(w + 2) = make_uint2(v.z, v.w);
         }
         if (threadIdx.x < GQ) reinterpret_cast<uint4 *>(sG)[threadIdx.x] = RG;
         __syncthreads();
-#if AMX_VT_LATE
         fetch(k + AMX_TF < L ? k + AMX_TF : k);
-#else
-        if (k + AMX_TF < L) fetch(k + AMX_TF);
-#endif
         if constexpr (AN) {
             // The analog stage couples the channels, so a lane takes whole frames: the
             // two lanes of a pair take every other frame (f = 2 i + half), both
@@ -326,24 +309,6 @@ __global__ void __launch_bounds__(AMX_BLOCK, 4) k_front1s(const ChainDev *__rest
 // every pair bit for bit), so the 32 769-entry half table (128 KB) sits in the LDS of one
 // 1024-thread workgroup per CU (4 waves per SIMD), loaded once; the workgroups then
 // stride over every chunk's 4-frame groups.
-#ifndef AMX_AN_VEC
-#define AMX_AN_VEC 1       // k_analog_h<true> where the plan allows it (0: always the general form)
-#endif
-#ifndef AMX_AN_DEPTH
-#define AMX_AN_DEPTH 3     // input blocks held in registers (2: one block ahead)
-#endif
-__device__ __forceinline__ void analog_load8(const float *src, int64_t f, int64_t n, bool vin, float (&x)[8]) {
-    if (f + 4 <= n && vin) {
-        const float4 u0 = *reinterpret_cast<const float4 *>(src);
-        const float4 u1 = *reinterpret_cast<const float4 *>(src + 4);
-        x[0] = u0.x; x[1] = u0.y; x[2] = u0.z; x[3] = u0.w;
-        x[4] = u1.x; x[5] = u1.y; x[6] = u1.z; x[7] = u1.w;
-    } else {
-#pragma unroll
-        for (int e = 0; e < 8; e++) x[e] = f + e / 2 < n ? src[e] : 0.0f;
-    }
-}
-
 // The workgroups stride over the 4096-frame blocks of all chunks in one sequence (block
 // b of the job -> its chunk by a scalar walk over the chunk list, monotone per
 // workgroup), so a chunk's last, partial round of blocks does not leave most workgroups
@@ -363,38 +328,9 @@ __global__ void __launch_bounds__(1024) k_analog_h(const ChainDev *__restrict__ 
     for (int i = threadIdx.x; i < AMX_HALF_LUT; i += 1024) s_tab[i] = lut_half[i];
     __syncthreads();
     const ChainDev &cd = *cdp;
-#if AMX_AN_DEPTH < 3
-    auto work = [&](const ChunkDev &ch, const float (&x)[8], int64_t ff) {
-        float t[8];
-#pragma unroll
-        for (int e = 0; e < 8; e++) {
-            const int q = (int)q_f32_to_s16_ffmpeg(x[e]);
-            // tanh(s) = sign(s) half[|s|]: half[] >= +0, so the sign is q's sign bit
-            // OR-ed into the value's (the plan checked lut[-s] == -lut[s] bit for bit)
-            const float v = s_tab[abs(q)];
-            t[e] = __int_as_float(__float_as_int(v) | (q & (int)0x80000000));
-        }
-        uint32_t o[4];
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            int16_t l, r;
-            analog_shelves(cd, t[2 * i], t[2 * i + 1], l, r);
-            o[i] = pack2(l, r);
-        }
-        uint32_t *dst = a16 + ch.loc_off + ff;
-        if (ff + 4 <= ch.n && (ch.loc_off & 3) == 0) {
-            *reinterpret_cast<uint4 *>(dst) = make_uint4(o[0], o[1], o[2], o[3]);
-        } else {
-#pragma unroll
-            for (int i = 0; i < 4; i++)
-                if (ff + i < ch.n) dst[i] = o[i];
-        }
-    };
-#endif
     constexpr int64_t BF = 1024 * 4;                   // frames per block
     int c = 0;
     int64_t cb0 = 0;                                    // first block of chunk c
-#if AMX_AN_DEPTH >= 3
     // Three register sets: the next two blocks' input (64 KB per CU) is in flight while
     // one is computed; one block ahead (32 KB per CU) held the kernel at ~3.6 TB/s.  For
     // the loads to stay in flight, every pass through the loop issues at least the
@@ -515,46 +451,6 @@ __global__ void __launch_bounds__(1024) k_analog_h(const ChainDev *__restrict__ 
             }
         }
     }
-#else
-    ChunkDev ch = chunks[0];
-    int64_t nb = (ch.n + BF - 1) / BF;
-    auto seek = [&](int64_t b) -> bool {                // workgroup-uniform
-        while (b >= cb0 + nb) {
-            cb0 += nb;
-            if (++c >= n_chunks) return false;
-            ch = chunks[c];
-            nb = (ch.n + BF - 1) / BF;
-        }
-        return true;
-    };
-    int64_t b = blockIdx.x;
-    if (!seek(b)) return;
-    ChunkDev cc = ch;
-    int64_t f = (b - cb0) * BF + threadIdx.x * 4;
-    // two register sets: the next block's input is in flight while one is computed
-    float xa[8], xb[8];
-    analog_load8(in + (cc.in_off + f) * 2, f, cc.n, (cc.in_off & 1) == 0, xa);
-    for (;;) {
-        b += gridDim.x;
-        const bool more = seek(b);
-        const ChunkDev cn = ch;
-        const int64_t fn = (b - cb0) * BF + threadIdx.x * 4;
-        if (more) analog_load8(in + (cn.in_off + fn) * 2, fn, cn.n, (cn.in_off & 1) == 0, xb);
-        if (f < cc.n) work(cc, xa, f);
-        if (!more) break;
-        cc = cn;
-        f = fn;
-        b += gridDim.x;
-        const bool more2 = seek(b);
-        const ChunkDev cn2 = ch;
-        const int64_t fn2 = (b - cb0) * BF + threadIdx.x * 4;
-        if (more2) analog_load8(in + (cn2.in_off + fn2) * 2, fn2, cn2.n, (cn2.in_off & 1) == 0, xa);
-        if (f < cc.n) work(cc, xb, f);
-        if (!more2) break;
-        cc = cn2;
-        f = fn2;
-    }
-#endif
 }
 
 // EQ pass 1 over the s16 stereo chain input a16 (after k_analog_h): the GEMV of
@@ -598,24 +494,14 @@ __global__ void __launch_bounds__(AMX_BLOCK, 4) k_gemv16(const ChainDev *__restr
         ilen[m] = rl[(t >> 2) + 64 * m];
     }
     uint4 R[2], RG;
-    // (AMX_VT_LATE, as vt_fetch / vt_put: the loads alone in fetch, the masks at the put,
+    // (as vt_fetch / vt_put: the loads alone in fetch, the masks at the put,
     // an unconditional fetch -- so the next tile's loads stay in flight over this tile)
     auto fetch = [&](int k) {
-#if AMX_VT_LATE
         RG = *reinterpret_cast<const uint4 *>(G + (int64_t)k * D + 2 * (t < GQ ? t : 0));
-#else
-        RG = t < GQ ? *reinterpret_cast<const uint4 *>(G + (int64_t)k * D + 2 * t) : make_uint4(0u, 0u, 0u, 0u);
-#endif
 #pragma unroll
         for (int m = 0; m < 2; m++) {
             const int n = k + c4;
             uint4 v = *reinterpret_cast<const uint4 *>(ip[m] + (n < ilen[m] ? k : 0));
-#if !AMX_VT_LATE
-            v.x = n < ilen[m] ? v.x : 0u;
-            v.y = n + 1 < ilen[m] ? v.y : 0u;
-            v.z = n + 2 < ilen[m] ? v.z : 0u;
-            v.w = n + 3 < ilen[m] ? v.w : 0u;
-#endif
             R[m] = v;
         }
     };
@@ -628,22 +514,16 @@ __global__ void __launch_bounds__(AMX_BLOCK, 4) k_gemv16(const ChainDev *__restr
 #pragma unroll
         for (int m = 0; m < 2; m++) {
             uint4 v = R[m];
-#if AMX_VT_LATE
             const int n = k + c4;
             v.x = n < ilen[m] ? v.x : 0u;
             v.y = n + 1 < ilen[m] ? v.y : 0u;
             v.z = n + 2 < ilen[m] ? v.z : 0u;
             v.w = n + 3 < ilen[m] ? v.w : 0u;
-#endif
             *reinterpret_cast<uint4 *>(s_in + ((t >> 2) + 64 * m) * AMX_G16_PITCH + c4) = v;
         }
         if (t < GQ) reinterpret_cast<uint4 *>(sG)[t] = RG;
         __syncthreads();
-#if AMX_VT_LATE
         fetch(k + AMX_TF < L ? k + AMX_TF : k);
-#else
-        if (k + AMX_TF < L) fetch(k + AMX_TF);
-#endif
 #pragma unroll 1
         for (int f = 0; f < AMX_TF; f++) {
             const uint32_t w = rp[f];
@@ -692,7 +572,7 @@ struct VRows {
     int len[2];           // frames in the row (an invalid row: 0)
 };
 
-// AMX_VT_LATE: the frames past a row's length are zeroed when the tile is put into LDS,
+// The frames past a row's length are zeroed when the tile is put into LDS,
 // not right after its load -- a select beside the load made the compiler wait for the
 // prefetched tile at once (vmcnt(0) right after the fetch: no overlap with the tile's
 // compute); and the fetch is unconditional (the last one re-reads the current tile), so
@@ -704,12 +584,7 @@ __device__ __forceinline__ void vt_fetch(vt4 (&R)[2], const uint32_t *__restrict
     for (int i = 0; i < 2; i++) {
         const int n = k + c4;
         const bool ok = n < vr.len[i];
-        vt4 v = *reinterpret_cast<const vt4 *>(src + vr.base[i] + (ok ? n : 0));
-#if !AMX_VT_LATE
-#pragma unroll
-        for (int e = 0; e < 4; e++) v[e] = n + e < vr.len[i] ? v[e] : 0u;
-#endif
-        R[i] = v;
+        R[i] = *reinterpret_cast<const vt4 *>(src + vr.base[i] + (ok ? n : 0));
     }
 }
 
@@ -717,26 +592,20 @@ __device__ __forceinline__ void vt_fetch(vt4 (&R)[2], const uint32_t *__restrict
 __device__ __forceinline__ void vt_put(uint32_t *lds, const vt4 (&R)[2], const VRows &vr, int k) {
     const int r0 = (threadIdx.x & 63) >> 2, c4 = 4 * (threadIdx.x & 3);
     vt4 v0 = R[0], v1 = R[1];
-#if AMX_VT_LATE
     const int n = k + c4;
 #pragma unroll
     for (int e = 0; e < 4; e++) {
         v0[e] = n + e < vr.len[0] ? v0[e] : 0u;
         v1[e] = n + e < vr.len[1] ? v1[e] : 0u;
     }
-#endif
     *reinterpret_cast<vt4 *>(lds + r0 * AMX_VT_PITCH + c4) = v0;
     *reinterpret_cast<vt4 *>(lds + (r0 + 16) * AMX_VT_PITCH + c4) = v1;
 }
 
-// the next tile's fetch: unconditional with AMX_VT_LATE (past the last tile it re-reads tile k)
+// the next tile's fetch: unconditional (past the last tile it re-reads tile k)
 __device__ __forceinline__ void vt_next(vt4 (&R)[2], const uint32_t *__restrict__ src, const VRows &vr,
                                         int k, int L) {
-#if AMX_VT_LATE
     vt_fetch(R, src, vr, k + AMX_TF < L ? k + AMX_TF : k);
-#else
-    if (k + AMX_TF < L) vt_fetch(R, src, vr, k + AMX_TF);
-#endif
 }
 
 __device__ __forceinline__ void vt_store(const uint32_t *lds, uint32_t *__restrict__ dst, const VRows &vr,
@@ -1039,7 +908,7 @@ static hipError_t front1s_t(const Launch &l, const uint32_t *in, const float *lu
             // s16 output; else (a tanh table that is not odd) k_front1s with the full table
             const int64_t wgs = l.an_blocks;
             const dim3 gh((unsigned)(wgs < cu_count() ? (wgs > 0 ? wgs : 1) : cu_count()));
-            const bool vec = AMX_AN_VEC && l.an_vec && (reinterpret_cast<uintptr_t>(in) & 15) == 0;
+            const bool vec = l.an_vec && (reinterpret_cast<uintptr_t>(in) & 15) == 0;
             if (vec)
                 hipLaunchKernelGGL(k_analog_h<true>, gh, dim3(1024), 0, l.stream, l.cd, l.chunks, l.n_chunks,
                                    reinterpret_cast<const float *>(in), l.lut_half, a16, l.an_blocks);

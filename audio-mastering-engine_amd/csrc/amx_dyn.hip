@@ -76,9 +76,7 @@ __device__ __forceinline__ uint32_t rms_floor(uint64_t S, uint32_t cnt, double r
 // AMX_RMS_N256: the tile of the LP = 256 form (48 / 44.1 kHz).  Measured (round 6,
 // profiles/r06m_rms_analog_ab.txt): 2048 frames (17 KB of prefix sums, 8 workgroups per
 // CU, 12.5 % halo) 1-2 us slower at C3 than 4096 (4 per CU, 6 % halo)
-#ifndef AMX_RMS_N256
 #define AMX_RMS_N256 4096
-#endif
 template <int LP, int N>
 __global__ void __launch_bounds__(AMX_BLOCK) k_rms(const ChainDev *__restrict__ cdp,
                                                    const ChunkDev *__restrict__ chunks,
@@ -709,9 +707,7 @@ __global__ void __launch_bounds__(64) k_envwide(const ChainDev *__restrict__ cdp
     }
 }
 
-#ifndef AMX_ENV_CHAIN_WAVES
 #define AMX_ENV_CHAIN_WAVES 2048    // k_envchain grid (waves loop over the head list)
-#endif
 template <bool RCP>
 __global__ void __launch_bounds__(64) k_envheads(const ChainDev *__restrict__ cdp,
                                                  const SegDev *__restrict__ es, int n_es,
@@ -1278,7 +1274,8 @@ static void env_launch_t(const DynLaunch &d, const uint16_t *m, double *ck, doub
     if (part == 0) {
         const int wg = d.env_wg >= 1 && d.env_wg <= AMX_ENV_WG ? d.env_wg : 1;
         const dim3 g0((unsigned)((d.n_es + 64 * wg - 1) / (64 * wg)), 3);
-        hipLaunchKernelGGL((k_env0<RCP>), g0, dim3(64 * wg), d.env_pin ? AMX_ENV_LDS_PIN : 0, d.st, d.cd,
+        // (a plan with envelope segments always pins: PlanHost::env_pin is 1 with multiband on)
+        hipLaunchKernelGGL((k_env0<RCP>), g0, dim3(64 * wg), AMX_ENV_LDS_PIN, d.st, d.cd,
                            d.chunks, d.es, d.n_es, m, d.tabs, ck, sv, ev, act, d.nloc, d.warm, flags);
         return;
     }

@@ -71,7 +71,7 @@ struct DynLaunch {
     int look, warm, Le, rcp;
     const double *tabs;
     hipStream_t st;
-    int env_wg, env_pin;         // k_env0: waves per workgroup, one workgroup per CU
+    int env_wg;                  // k_env0: waves per workgroup (one workgroup per CU)
 };
 hipError_t launch_rms(const DynLaunch &d, const int16_t *bands, uint16_t *m, int *bact);
 // C > 2 channels (round 6): the bands of a stream sub-plan (schunks, snloc), r / the
@@ -192,9 +192,7 @@ struct LnArgs {
 #define AMX_LN_RING 40320          // frame_size(192000, 210): the limiter ring, frames
 #define AMX_LN_WIN 2048            // ring frames compared at a segment boundary
 #define AMX_LN_REC (16 + 2 * AMX_LN_WIN)   // doubles of one boundary state record
-#ifndef AMX_LP_NT
 #define AMX_LP_NT 256    // lanes of a k_lp_seg / k_lp_walk workgroup (amx_loudnorm.hip)
-#endif
 struct LpArgs {
     int64_t n;                    // 192 kHz frames
     int64_t S0;                   // first output frame of the FINAL (flush) frame

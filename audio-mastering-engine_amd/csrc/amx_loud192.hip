@@ -41,18 +41,10 @@ namespace amx {
 
 #define UP_TAPS 32
 #define UP_C 15            // center tap
-#ifndef AMX_UP_TB
 #define AMX_UP_TB 8        // input frames per window block (STATIC path)
-#endif
-#ifndef AMX_UP_SB
 #define AMX_UP_SB 6        // sched_barrier mask: VALU + SALU may cross, scalar loads may not
-#endif
-#ifndef UP_DOT
 #define UP_DOT up_dot2      // packed-pair form of the fast kernel's dot products
-#endif
-#ifndef AMX_UP_WAVES
 #define AMX_UP_WAVES 4     // waves per SIMD the register budget must allow
-#endif
 
 __device__ __forceinline__ float up_sample(uint32_t w, int ch) {
     return (float)(ch ? hi16(w) : lo16(w)) * (1.0f / 32768.0f);

@@ -66,9 +66,6 @@ __device__ __forceinline__ float ln_dot(const float *w, const float *__restrict_
 
 typedef float ln_f2 __attribute__((ext_vector_type(2)));
 typedef unsigned lp_u4 __attribute__((ext_vector_type(4)));
-#ifndef AMX_LP_HANDOFF
-#define AMX_LP_HANDOFF 1     // k_lp_seg's boundary records: sc1 stores + one acquire (0: __threadfence form)
-#endif
 
 // ln_dot with the 8 chains as 4 packed pairs (v_pk_fma_f32 / v_pk_add_f32): the same
 // operations lane by lane, the first term a fused multiply-add onto 0 as in ln_dot
@@ -98,20 +95,14 @@ __device__ __forceinline__ float ln_dot2(const float *w, P h) {
 // stores had a 32 L-byte stride (one 16-B piece per 128-B line per instruction at 48 kHz:
 // the writes, 461 MB for a 5-min track, ran at ~2.4 TB/s).  A workgroup whose 256 x 4
 // frames are all in range stages its outputs in LDS and writes them as one contiguous
-// block, 16 B per lane per instruction (AMX_LN_UPS_LDS; the others store directly).
-#ifndef AMX_LN_UPS_LDS
-#define AMX_LN_UPS_LDS 1
-#endif
-#ifndef AMX_LN_UPS_PH
-#define AMX_LN_UPS_PH 1
-#endif
+// block, 16 B per lane per instruction (the others store directly).
 template <int L>
 __global__ void __launch_bounds__(AMX_BLOCK) k_ln_up_static(const uint32_t *__restrict__ x, int64_t n_in,
                                                             const float *__restrict__ bank, int64_t j0, int64_t j1,
                                                             float *__restrict__ u, const int32_t *__restrict__ gate) {
     if (AMX_LN_GATED(gate)) return;
     constexpr int NW = LN_TAPS + LN_UPF - 1;
-    constexpr bool STAGE = AMX_LN_UPS_LDS && (L % 2 == 0);
+    constexpr bool STAGE = L % 2 == 0;
     constexpr int TF = 2 * L * LN_UPF;                 // floats a thread produces
     __shared__ __attribute__((aligned(16))) float s_o[STAGE ? AMX_BLOCK * TF : 4];
 
@@ -158,32 +149,24 @@ __global__ void __launch_bounds__(AMX_BLOCK) k_ln_up_static(const uint32_t *__re
         const int64_t fw = f0 + b0 * LN_UPF;
         const bool whole = STAGE && b0 + AMX_BLOCK <= nblk && fw * L >= j0 &&
                            (fw + (int64_t)AMX_BLOCK * LN_UPF) * L <= j1 && fw + (int64_t)AMX_BLOCK * LN_UPF <= f1;
-#if AMX_LN_UPS_PH
         // a (frame, phase)'s 32 bank taps are scalar operands loaded just before its two
         // dots: the load address depends on the previous dot's result, so the compiler
         // cannot hoist every frame's and phase's taps together (all 32 L at once: 128 SGPRs
         // at L = 4, spilled to VGPR lanes, 332 v_readlane per pass beside 512 v_pk_fma)
         typedef const __attribute__((address_space(4))) float *ConstF;
         float dep = 0.0f;
-#endif
 #pragma unroll
         for (int k = 0; k < LN_UPF; k++) {
             const int64_t f = fb + k;
             float o[2 * L];
 #pragma unroll
             for (int ph = 0; ph < L; ph++) {
-#if AMX_LN_UPS_PH
                 uint64_t bp = reinterpret_cast<uint64_t>(bank + ph * LN_TAPS);
                 asm volatile("" : "+s"(bp) : "v"(dep));
                 const ConstF h = (ConstF)bp;
-#else
-                const float *h = bank + ph * LN_TAPS;
-#endif
                 o[2 * ph] = ln_dot2(w0 + k, h);
                 o[2 * ph + 1] = ln_dot2(w1 + k, h);
-#if AMX_LN_UPS_PH
                 dep = o[2 * ph + 1];
-#endif
             }
             if constexpr (STAGE) {
                 if (whole) {
@@ -1286,10 +1269,7 @@ __device__ __forceinline__ int lp_seg_start(const LpArgs &a, int k) {
 // slot loops (fills, envelopes, output) and its peak scans are LP_NT wide, so a release's
 // 19 200 slots or a frame's scan take 1 / LP_NW of one wave's dependent memory round
 // trips; the scalar state is workgroup-uniform (every lane holds it).
-#ifndef AMX_LP_NT
-#define AMX_LP_NT 256
-#endif
-#define LP_NT AMX_LP_NT
+#define LP_NT AMX_LP_NT         // 256 (amx_internal.hpp)
 #define LP_NW (LP_NT / 64)
 #define LP_STW (LP_NT + 16)      // one channel's scan row: a group and its 12-position look-ahead
 
@@ -1307,34 +1287,24 @@ struct LpWave {
     double d0, off;
 };
 
-// a barrier only a multi-wave workgroup needs (one wave's lanes run in lock step)
-__device__ __forceinline__ void lp_wg_barrier() {
-#if LP_NW > 1
-    __syncthreads();
-#endif
-}
+// the workgroup barrier where a single wave would need none (its lanes run in lock step)
+__device__ __forceinline__ void lp_wg_barrier() { __syncthreads(); }
 
 // the workgroup barrier after ring stores another wave reads next: every wave's stores
 // have completed (vmcnt) before it arrives
 __device__ __forceinline__ void lp_sync_ring() {
-#if LP_NW > 1
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
     __syncthreads();
 }
 
 // workgroup votes (uniform control flow only): the waves' ballots through LDS
 __device__ __forceinline__ void lp_vote(const LpWave &W, bool p, unsigned long long (&m)[LP_NW]) {
     const unsigned long long b = __ballot(p);
-#if LP_NW == 1
-    m[0] = b;
-#else
     __syncthreads();                       // the previous vote's readers are done
     if ((threadIdx.x & 63) == 0) W.sv[threadIdx.x >> 6] = b;
     __syncthreads();
 #pragma unroll
     for (int w = 0; w < LP_NW; w++) m[w] = W.sv[w];
-#endif
 }
 // the first set bit at index >= from of an LP_NT-bit vote, or -1
 __device__ __forceinline__ int lp_next(const unsigned long long (&m)[LP_NW], int from) {
@@ -1353,30 +1323,15 @@ __device__ __forceinline__ int lp_first(const LpWave &W, bool p) {
     lp_vote(W, p, m);
     return lp_next(m, 0);
 }
-// workgroup max / sum (the waves' reductions through the vote scratch)
+// workgroup max (the waves' reductions through the vote scratch)
 __device__ __forceinline__ double lp_wg_max(const LpWave &W, double v) {
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) v = fmax(v, __shfl_xor(v, o));
-#if LP_NW > 1
     __syncthreads();
     if ((threadIdx.x & 63) == 0) W.sv[threadIdx.x >> 6] = (unsigned long long)__double_as_longlong(v);
     __syncthreads();
 #pragma unroll
     for (int w = 0; w < LP_NW; w++) v = fmax(v, __longlong_as_double((long long)W.sv[w]));
-#endif
-    return v;
-}
-__device__ __forceinline__ int lp_wg_sum(const LpWave &W, int v) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) v += __shfl_xor(v, o);
-#if LP_NW > 1
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) W.sv[threadIdx.x >> 6] = (unsigned long long)(unsigned)v;
-    __syncthreads();
-    v = 0;
-#pragma unroll
-    for (int w = 0; w < LP_NW; w++) v += (int)(unsigned)W.sv[w];
-#endif
     return v;
 }
 
@@ -1480,15 +1435,10 @@ __device__ __forceinline__ void lp_refill(const LpArgs &a, LpWave &W, int phi) {
 // multiply k slots from e0 by env(i) (af_loudnorm's envelope loops).  The k slots are
 // distinct, so the values of 4 groups of LP_NT are loaded before any of them is written
 // (one memory round trip per 4 LP_NT slots), and no pass reads a slot another pass
-// writes: the ring is synchronised once, after the last pass (AMX_LP_ENV_SYNC1; a sync
+// writes: the ring is synchronised once, after the last pass (a sync
 // per pass drained every pass's stores before the next one's loads -- a release's 19 200
 // slots paid 19 store drains and barriers)
-#ifndef AMX_LP_ENV_SYNC1
-#define AMX_LP_ENV_SYNC1 1
-#endif
-#ifndef AMX_LP_EG
 #define AMX_LP_EG 4              // groups of LP_NT slots per envelope pass (one memory round trip)
-#endif
 template <class F>
 __device__ __forceinline__ void lp_env(const LpArgs &a, LpWave &W, int e0, int k, F env) {
     for (int i00 = 0; i00 < k; i00 += AMX_LP_EG * LP_NT) {
@@ -1513,13 +1463,8 @@ __device__ __forceinline__ void lp_env(const LpArgs &a, LpWave &W, int e0, int k
                 atomicOr(&W.flags[s[p] >> 5], 1u << (s[p] & 31));
             }
         }
-#if !AMX_LP_ENV_SYNC1
-        lp_sync_ring();
-#endif
     }
-#if AMX_LP_ENV_SYNC1
     if (k > 0) lp_sync_ring();
-#endif
 }
 
 __device__ __forceinline__ int lp_env_end(int e0, int k) {
@@ -1527,9 +1472,7 @@ __device__ __forceinline__ int lp_env_end(int e0, int k) {
     return e >= LP_RS ? e - LP_RS : e;
 }
 
-#ifndef AMX_LP_PD
-#define AMX_LP_PD 4              // (measurement builds: scripts/build_var.py)
-#endif
+#define AMX_LP_PD 4
 #define LP_PD AMX_LP_PD          // lp_detect: groups of LP_NT positions loaded together
 // one group's values: LP_NT positions from slot s0
 __device__ __forceinline__ double2 lp_grp(const LpArgs &a, const LpWave &W, int s0, int lane) {
@@ -1550,9 +1493,6 @@ __device__ __forceinline__ double2 lp_grp(const LpArgs &a, const LpWave &W, int 
 // skipped without loading a value, LP_NT groups per vote
 __device__ __forceinline__ int lp_detect(const LpArgs &a, LpWave &W, int smp, int count, double &peak_value,
                          int &peak_slot) {
-#ifdef AMX_LPV_NODETECT        // measurement variant: the limiter never engages (wrong output)
-    return -1;
-#endif
     const int lane = threadIdx.x;
     int slot0 = W.f.lbi + smp + LP_ATT;
     if (slot0 >= LP_RS) slot0 -= LP_RS;
@@ -1708,7 +1648,6 @@ __device__ __forceinline__ void lp_emit(const LpArgs &a, const LpWave &W) {
     }
 }
 
-#define LP_SPARSE_MAX 4096       // multiplied slots in a frame above which lp_emit_sparse emits densely
 // the bits of flag word w inside slots [lo, lo + len) mod LP_RS
 __device__ __forceinline__ unsigned lp_range_bits(int w, int lo, int len) {
     unsigned m = 0u;
@@ -1725,18 +1664,13 @@ __device__ __forceinline__ unsigned lp_range_bits(int w, int lo, int len) {
 
 // the output of the frame where k_lp_fill already wrote every position's unlimited
 // value: only the slots the limiter multiplied differ -- their ring values, clamped, s16.
-// AMX_LP_EMIT_RANGE (default): the frame positions from the first to the last flagged
-// one, a lane per position and AMX_LP_EM groups of LP_NT per pass, each lane loading its
-// ring slot unconditionally (slot 0 when unflagged) and storing only a flagged one -- one
-// memory round trip per pass.  The per-word form below walked a word's set bits with a
-// load each: a burst frame's thousands of flagged slots cost ~50 us of dependent loads
-#ifndef AMX_LP_EMIT_RANGE
-#define AMX_LP_EMIT_RANGE 1
-#endif
-#ifndef AMX_LP_EM
+// The frame positions from the first to the last flagged one, a lane per position and
+// AMX_LP_EM groups of LP_NT per pass, each lane loading its ring slot unconditionally
+// (slot 0 when unflagged) and storing only a flagged one -- one memory round trip per
+// pass.  (A per-word form walked a word's set bits with a load each: a burst frame's
+// thousands of flagged slots cost ~50 us of dependent loads.)
 #define AMX_LP_EM 8
-#endif
-__device__ __forceinline__ void lp_emit_range(const LpArgs &a, const LpWave &W) {
+__device__ __forceinline__ void lp_emit_sparse(const LpArgs &a, const LpWave &W) {
     const int nb = W.f.nb, lbi = W.f.lbi;
     // the first and last flagged frame positions (i = slot - lbi mod LP_RS, i < nb).  The
     // frame's range (nb <= LP_FR, far below LP_RS - 32) never holds both ends of itself in
@@ -1778,38 +1712,6 @@ __device__ __forceinline__ void lp_emit_range(const LpArgs &a, const LpWave &W) 
                 if (fabs(o1) > ceiling) o1 = ceiling * (o1 < 0 ? -1 : 1);
                 y[W.f.base + i] = pack2(ln_s16(o0), ln_s16(o1));
             }
-        }
-    }
-}
-
-__device__ __forceinline__ void lp_emit_sparse(const LpArgs &a, const LpWave &W) {
-#if AMX_LP_EMIT_RANGE
-    lp_emit_range(a, W);
-    return;
-#endif
-    const int nb = W.f.nb, lbi = W.f.lbi;
-    int cnt = 0;
-    for (int w = threadIdx.x; w < LP_FW; w += LP_NT) cnt += __popc(W.flags[w] & lp_range_bits(w, lbi, nb));
-    cnt = lp_wg_sum(W, cnt);
-    if (cnt == 0) return;
-    if (cnt > LP_SPARSE_MAX) {
-        lp_emit(a, W);
-        return;
-    }
-    const double ceiling = a.ceiling;
-    uint32_t *y = reinterpret_cast<uint32_t *>(a.y);
-    for (int w = threadIdx.x; w < LP_FW; w += LP_NT) {
-        unsigned m = W.flags[w] & lp_range_bits(w, lbi, nb);
-        while (m) {
-            const int s = 32 * w + __ffs(m) - 1;
-            m &= m - 1u;
-            int i = s - lbi;
-            if (i < 0) i += LP_RS;
-            const double2 v = W.ring[s];
-            double o0 = v.x, o1 = v.y;
-            if (fabs(o0) > ceiling) o0 = ceiling * (o0 < 0 ? -1 : 1);
-            if (fabs(o1) > ceiling) o1 = ceiling * (o1 < 0 ? -1 : 1);
-            y[W.f.base + i] = pack2(ln_s16(o0), ln_s16(o1));
         }
     }
 }
@@ -1911,9 +1813,6 @@ __device__ __forceinline__ void lp_call(const LpArgs &a, LpWave &W, int emit) {
             }
         }
     } while (smp < nb);
-#ifdef AMX_LPV_NOEMIT          // measurement variant: no output (wrong output)
-    emit = 0;
-#endif
     if (emit == 1) lp_emit_sparse(a, W);
     else if (emit == 2) lp_emit(a, W);
 }
@@ -1950,7 +1849,6 @@ __device__ __forceinline__ void lp_snapshot(const LpArgs &a, const LpWave &W, do
         out |= m != 0u;
     }
     const bool dirty = lp_first(W, out) >= 0;
-#if AMX_LP_HANDOFF
     // the record goes out write-through (sc1, 16-B buffer stores): k_lp_seg's other
     // workgroups read it in this launch (lp_arrive), on any XCD, with no release fence.
     // The window's values are loaded half at a time before they are stored (two memory
@@ -1973,40 +1871,13 @@ __device__ __forceinline__ void lp_snapshot(const LpArgs &a, const LpWave &W, do
         for (int q = 0; q < NH; q++) {
             int s = w0 + lane + (h * NH + q) * LP_NT;
             if (s >= LP_RS) s -= LP_RS;
-#ifdef AMX_LPV_NOSNAP          // measurement variant: the window's values not loaded (wrong output)
-            v[q] = make_double2(0.0, 0.0);
-#else
             v[q] = lp_val(a, W, s);
-#endif
         }
 #pragma unroll
         for (int q = 0; q < NH; q++)
             __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(lp_u4, v[q]), rr,
                                                    (16 + 2 * (lane + (h * NH + q) * LP_NT)) * (int)sizeof(double), 0, 16);
     }
-#else
-    if (lane == 0) {
-        rec[0] = W.mode;
-        rec[1] = W.env_cnt;
-        rec[2] = W.env_index;
-        rec[3] = W.attack_length;
-        rec[4] = W.gr0;
-        rec[5] = W.gr1;
-        rec[6] = W.f.phi;
-        rec[LP_DIRTY] = dirty ? 1.0 : 0.0;
-    }
-    for (int j = lane; j < LP_WIN; j += LP_NT) {
-        int s = w0 + j;
-        if (s >= LP_RS) s -= LP_RS;
-#ifdef AMX_LPV_NOSNAP          // measurement variant: the window's values not loaded (wrong output)
-        const double2 v = make_double2(0.0, 0.0);
-#else
-        const double2 v = lp_val(a, W, s);
-#endif
-        rec[16 + 2 * j] = v.x;
-        rec[17 + 2 * j] = v.y;
-    }
-#endif
 }
 
 // the same state back into a wave (every window slot flagged with its recorded value)
@@ -2042,7 +1913,6 @@ __device__ __forceinline__ bool lp_same(const LpWave &W, const double *A, const 
     bool diff = A[LP_DIRTY] != 0.0 || B[LP_DIRTY] != 0.0 || (int)A[0] != (int)B[0];
     if ((int)A[0] != LO_OUT || (int)B[0] != LO_OUT)
         for (int q = 0; q < 6; q++) diff |= !lp_bits_eq(A[q], B[q]);
-#if AMX_LP_HANDOFF
     // every load issued before any compare (one round trip, not one per pass)
     constexpr int NC = 2 * LP_WIN / LP_NT, NH = NC / 2;
 #pragma unroll 1
@@ -2056,9 +1926,6 @@ __device__ __forceinline__ bool lp_same(const LpWave &W, const double *A, const 
 #pragma unroll
         for (int q = 0; q < NH; q++) diff |= !lp_bits_eq(x[q], y[q]);
     }
-#else
-    for (int j = threadIdx.x; j < 2 * LP_WIN; j += LP_NT) diff |= !lp_bits_eq(A[16 + j], B[16 + j]);
-#endif
     return lp_first(W, diff) < 0;
 }
 
@@ -2067,7 +1934,6 @@ __device__ __forceinline__ bool lp_same(const LpWave &W, const double *A, const 
 // (every wave's record stores are released -- its own fence -- before lane 0 counts
 // the arrival; the count is broadcast through LDS)
 __device__ __forceinline__ void lp_arrive(const LpArgs &a, const LpWave &W, int j) {
-#if AMX_LP_HANDOFF
     // the hand-off of DESIGN.md §3.7 / the guide's R1 form: the records were stored sc1
     // (lp_snapshot); every wave drains its stores, then one relaxed agent-scope count;
     // the second arriver acquires once (one lane's fence, its wait, the barrier) and reads
@@ -2087,18 +1953,6 @@ __device__ __forceinline__ void lp_arrive(const LpArgs &a, const LpWave &W, int 
         const bool same = lp_same(W, a.recE + (int64_t)(j - 1) * LP_REC, a.recG + (int64_t)j * LP_REC);
         if (threadIdx.x == 0) a.match[j] = same ? 1 : 0;
     }
-#else
-    __threadfence();
-    __syncthreads();
-    if (threadIdx.x == 0) W.sv[0] = (unsigned long long)(unsigned)atomicAdd(&a.cnt[j], 1);
-    __syncthreads();
-    const int old = (int)(unsigned)W.sv[0];
-    if (old == 1) {
-        __threadfence();
-        const bool same = lp_same(W, a.recE + (int64_t)(j - 1) * LP_REC, a.recG + (int64_t)j * LP_REC);
-        if (threadIdx.x == 0) a.match[j] = same ? 1 : 0;
-    }
-#endif
 }
 
 __device__ __forceinline__ void lp_wave_init(const LpArgs &a, LpWave &W, double2 *ring, unsigned *flags,
@@ -2122,9 +1976,7 @@ __device__ __forceinline__ void lp_wave_init(const LpArgs &a, LpWave &W, double2
 // outside [u_lo, u_hi) or past the track.  The fill is lp_val's expression term for
 // term: u (gain ramp) offset for INNER positions, u d0 offset below the ring's first
 // fill, u G_T offset for the positions FINAL emits.  One wave per 64-position block.
-#ifndef AMX_LPF_GRID
 #define AMX_LPF_GRID 65536
-#endif
 __global__ void __launch_bounds__(256) k_lp_fill(LpArgs a, int64_t y_lo, int64_t y_hi, int64_t u_lo, int64_t u_hi) {
     if ((a.ctl[0] != 0 && a.ctl[0] != 4) || a.T < 1) return;
     if (a.ctl[0] == 4) {
@@ -2252,10 +2104,8 @@ __global__ void __launch_bounds__(256) k_lp_fill(LpArgs a, int64_t y_lo, int64_t
 }
 
 // every segment at once (persistent waves): from rest Wf frames before its start
-#ifndef AMX_LP_WPE
 #define AMX_LP_WPE 3             // k_lp_seg waves per SIMD the register budget allows (168
                                  // VGPRs, a 300-B spill; 2: C5 dynamic 43.0 vs 40.9 ms)
-#endif
 __global__ void __launch_bounds__(LP_NT) __attribute__((amdgpu_waves_per_eu(AMX_LP_WPE))) k_lp_seg(LpArgs a) {
     if (a.ctl[0] != 0 && a.ctl[0] != 4) return;
     const int kh = a.ctl[0] == 4 ? a.ctl[4] : 0;     // a quiet start: k_ln_dyn ran segments < kh

@@ -266,7 +266,7 @@ int amx_run_stage(amx_plan *p, int32_t stage, const float *d_in, int16_t *d_out,
     amx::DynLaunch dl{p->d_cd,    p->d_chunks, p->n_chunks, p->d_esegs, p->n_es,
                       p->d_eseg0, p->d_neseg,  p->nloc,     p->max_chunk_n, p->cd.look,
                       p->warm,    p->Le,       p->cd.env_rcp, p->d_tabs, st,
-                      p->env_wg,  p->env_pin};
+                      p->env_wg};
     switch (stage) {
     case AMX_STAGE_FRONT1:
         if (p->mono16) {
@@ -381,16 +381,16 @@ struct LnLayout {
     int64_t total = 0;
 };
 // INNER frames, segments of Fs frames each warmed up Wf frames (AMX_LN_WARM, default 2)
-// before its start, at most P persistent k_lp_seg workgroups of AMX_LP_NT lanes (AMX_LN_P;
-// default 3072 waves: three per SIMD, k_lp_seg's register budget).  Fs (AMX_LN_SEG overrides) is the smallest >= 2 whose segments fit the P waves: a
+// before its start, at most P persistent k_lp_seg workgroups of AMX_LP_NT lanes (3072
+// waves: three per SIMD, k_lp_seg's register budget).  Fs (AMX_LN_SEG overrides) is the
+// smallest >= 2 whose segments fit the P waves: a
 // wave then runs one segment, Fs + Wf frames (r04m: a 5-min track 11.9 -> 9.1 ms per
 // dynamic step from Fs 4 / Wf 3 / 1024 waves); a longer track takes longer segments, so
 // the warm-up share Wf / Fs shrinks instead of waves running several segments each.
 LnLayout ln_layout(int64_t n192, int64_t u_frames = -1, int p_cap = -1) {
     LnLayout l;
     l.Wf = 2;
-    int pmax = 3072 / (AMX_LP_NT / 64);
-    if (const char *ev = std::getenv("AMX_LN_P")) pmax = std::max(64, std::atoi(ev));
+    const int pmax = 3072 / (AMX_LP_NT / 64);
     if (n192 >= LN_FIRST_FRAMES) {
         l.T = (int)((n192 - LN_FIRST_FRAMES + 19199) / 19200);
         l.nb_last = l.T > 0 ? (int)(n192 - LN_FIRST_FRAMES - 19200LL * (l.T - 1)) : 0;
@@ -624,13 +624,11 @@ int ln_args(amx_plan *p, int32_t track, const amx_loudnorm_desc *d, const double
     a.lp_tstop = INT_MAX;
     q.kb = 0;
     q.ke = q.K;
-    // k_lp_fill + the skipping scan + the sparse emit (AMX_LP_FILL=0: the dense form, for
-    // A/B measurements)
+    // k_lp_fill + the skipping scan + the sparse emit (AMX_LP_FILL=0: the dense form, the
+    // tests' cross-check of the sparse one), with FINAL's bound
     const char *fe = std::getenv("AMX_LP_FILL");
     q.bm = (fe && std::atoi(fe) == 0) ? nullptr : reinterpret_cast<double *>(w + lo.o_bm);
-    // FINAL's bound (AMX_LP_FINAL_SKIP=0: FINAL's frames scan every group, for A/B)
-    const char *fs = std::getenv("AMX_LP_FINAL_SKIP");
-    q.bmF = (q.bm && !(fs && std::atoi(fs) == 0)) ? reinterpret_cast<double *>(w + lo.o_bmF) : nullptr;
+    q.bmF = q.bm ? reinterpret_cast<double *>(w + lo.o_bmF) : nullptr;
     return AMX_OK;
 }
 }  // namespace
@@ -1244,7 +1242,7 @@ int amx_mc_run_chunks(amx_mc_plan *m, const void *d_in, int16_t *d_out, void *d_
     amx::DynLaunch dl{pc->d_cd,    pc->d_chunks, pc->n_chunks, pc->d_esegs, pc->n_es,
                       pc->d_eseg0, pc->d_neseg,  pc->nloc,     pc->max_chunk_n, pc->cd.look,
                       pc->warm,    pc->Le,       pc->cd.env_rcp, pc->d_tabs, st,
-                      pc->env_wg,  pc->env_pin};
+                      pc->env_wg};
     const int16_t *bands = wsp<int16_t>(wb, pb->o_bands);
     uint16_t *mframe = wsp<uint16_t>(wc, pc->o_m);
     int *bact = wsp<int>(wc, pc->o_eflags) + AMX_ENV_BACT;

@@ -242,24 +242,6 @@ int swr_bank(int in_rate, int out_rate, float *bank) {
 
 PlanKnobs PlanKnobs::from_env() {
     PlanKnobs k;
-    const auto floor128 = [](const char *ev) { return std::max(128, std::atoi(ev)) / 128 * 128; };
-    if (const char *ev = std::getenv("AMX_ENV_LE")) {          // (measurements only)
-        k.env_le_set = true;
-        k.env_le = std::max(128, std::atoi(ev) / 128 * 128);
-    }
-    if (const char *ev = std::getenv("AMX_UP_LOUT")) k.up_lout = std::max(16, std::atoi(ev));
-    k.k192_native = std::getenv("AMX_K192_NATIVE") != nullptr;
-    if (const char *ev = std::getenv("AMX_ENV_GUESS")) k.env_guess = std::atoi(ev) != 0;
-    if (const char *ev = std::getenv("AMX_ENV_WG")) k.env_wg = std::atoi(ev);
-    if (const char *ev = std::getenv("AMX_ENV_LEMIN")) {
-        k.env_lemin_set = true;
-        k.env_lemin = floor128(ev);
-    }
-    if (const char *ev = std::getenv("AMX_ENV_LEMIN2")) {
-        k.env_lemin2_set = true;
-        k.env_lemin2 = floor128(ev);
-    }
-    if (const char *ev = std::getenv("AMX_ENV_BANDTAB")) k.env_bandtab = std::atoi(ev);
     if (const char *ev = std::getenv("AMX_UP_POLY")) k.up_poly = std::atoi(ev) != 0;
     // (tests: AMX_F1 = 2 runs the full-table form k_front1s, the path a table that is
     // not odd takes)
@@ -338,10 +320,10 @@ void Builder::measurement_stream() {
             p->upL = p->upM = 1;
             kfs = fs;
         } else {
-            // ~384 192 kHz outputs per K segment, a divisor of the 100 ms hop (19200)
+            // ~480 192 kHz outputs per K segment, a divisor of the 100 ms hop (19200)
             // where one exists, so a segment lies inside one hop (no hop split)
             const int hop192 = (kfs + 5) / 10;
-            const int target = knobs.up_lout;   // 480 (AMX_UP_LOUT overrides, for measurements)
+            const int target = 480;
             p->up_pc = amx::swr_phases(fs, kfs);
             amx::swr_filter(fs, kfs, &p->up_taps, &p->up_alloc, nullptr);
             amx::swr_incr(fs, kfs, &p->up_src, &p->up_dst);
@@ -371,20 +353,18 @@ void Builder::measurement_stream() {
         // k_ln_upsample produce exactly that (every other tap adds 0).  The measurement
         // takes the resampler path with that identity (L = M = 1, k_up<1>): one pass over
         // the samples -- K filter, peaks and the hop pieces' energy terms -- where the
-        // native path ran the GEMV and then the filter again (k_kw1 + k_kw2).
-        // AMX_K192_NATIVE=1 keeps the native path (measurements).
+        // native path (still taken by a rate loudnorm is refused on, above) ran the GEMV
+        // and then the filter again (k_kw1 + k_kw2).
         bank.assign(32, 0.0f);
         bank[15] = 1.0f;
-        if (!knobs.k192_native) {
-            p->resamp = 1;
-            p->upL = p->upM = 1;
-            p->up_pc = 1;
-            p->up_taps = p->up_alloc = 32;
-            p->up_src = p->up_dst = 1;
-            p->up_lin = 0;
-            p->upLin = p->upLout = 480;            // 40 K segments per 100 ms hop
-            p->up_static = 1;
-        }
+        p->resamp = 1;
+        p->upL = p->upM = 1;
+        p->up_pc = 1;
+        p->up_taps = p->up_alloc = 32;
+        p->up_src = p->up_dst = 1;
+        p->up_lin = 0;
+        p->upLin = p->upLout = 480;            // 40 K segments per 100 ms hop
+        p->up_static = 1;
     }
     p->hop = (kfs + 5) / 10;                   // libebur128 samples_in_100ms at 192 kHz
     {
@@ -563,7 +543,7 @@ int Builder::compressor_tables() {
     cd.env_R = R;
     cd.env_rA = 1.0 / A;
     cd.env_rR = 1.0 / R;
-    cd.env_guess = knobs.env_guess;                     // 1 (measurements: AMX_ENV_GUESS=0)
+    cd.env_guess = 1;                                   // k_env0 still reads it
     cd.env_rcp = 1;
     for (size_t i = 0; i < (size_t)3 * 3 * 32769 && cd.env_rcp; i += 1) {
         if (i % (3 * 32769) >= 32769) continue;
@@ -593,40 +573,28 @@ int Builder::count_tracks() {
 // envelope segment sizing: Le per active-band count, k_env0's placement, the warm-up
 void Builder::envelope_sizing() {
     if (!p->mb) return;
-    // k_env0 runs one resident wave set: env_wg waves per CU (one workgroup per CU),
-    // Le the shortest multiple of 128 (>= 1024) whose segments fit it, so no CU runs
-    // waves in turn and the warm-up share W / Le shrinks as the job grows
-    // (AMX_ENV_WG = 0 is the single-wave-workgroup launch)
-    const int wg = knobs.env_wg;
-    const int64_t le_min = knobs.env_lemin;                  // 1024 (measurements: AMX_ENV_LEMIN)
-    if (wg > 0) {
-        p->env_wg = std::min(wg, 4);
-        p->env_pin = 1;
-        if (!knobs.env_le_set) {
-            // segments per band: W waves of one band per CU, the CUs shared by the t
-            // bands that are active (t = 3: every band; the tables for 1 and 2 active
-            // bands have shorter segments, floor 512 frames; AMX_ENV_BANDTAB=0 keeps
-            // the 3-band table for every count)
-            const int bandtab = knobs.env_bandtab;
-            int64_t total = 0;
-            for (int c = 0; c < n_chunks; c++) total += chunks[c].frames;
-            for (int t = 3; t >= 1; t--) {
-                const int64_t fit = (int64_t)(ncu / t) * 64 * p->env_wg;
-                int64_t lo = (t == 3 || knobs.env_lemin_set) ? le_min : 512;
-                if (knobs.env_lemin2_set && t < 3) lo = knobs.env_lemin2;           // (measurements)
-                int64_t Le = std::max<int64_t>(lo, (total / fit + 127) / 128 * 128);
-                for (;; Le += 128) {
-                    int64_t ne = 0;
-                    for (int c = 0; c < n_chunks; c++) ne += (chunks[c].frames + Le - 1) / Le;
-                    if (ne <= fit || Le >= (int64_t)1 << 24) break;
-                }
-                p->Le_t[t] = (t == 3 || bandtab) ? (int)Le : p->Le_t[3];
-            }
-            p->Le = p->Le_t[3];
+    // k_env0 runs one resident wave set: 2 waves per CU (one workgroup per CU), Le the
+    // shortest multiple of 128 whose segments fit it, so no CU runs waves in turn and the
+    // warm-up share W / Le shrinks as the job grows
+    p->env_wg = 2;
+    p->env_pin = 1;
+    // segments per band: the waves of one band per CU, the CUs shared by the t bands that
+    // are active (t = 3: every band, floor 1024 frames; the tables for 1 and 2 active
+    // bands have shorter segments, floor 512)
+    int64_t total = 0;
+    for (int c = 0; c < n_chunks; c++) total += chunks[c].frames;
+    for (int t = 3; t >= 1; t--) {
+        const int64_t fit = (int64_t)(ncu / t) * 64 * p->env_wg;
+        const int64_t lo = t == 3 ? 1024 : 512;
+        int64_t Le = std::max<int64_t>(lo, (total / fit + 127) / 128 * 128);
+        for (;; Le += 128) {
+            int64_t ne = 0;
+            for (int c = 0; c < n_chunks; c++) ne += (chunks[c].frames + Le - 1) / Le;
+            if (ne <= fit || Le >= (int64_t)1 << 24) break;
         }
+        p->Le_t[t] = (int)Le;
     }
-    for (int t = 1; t <= 3; t++)
-        if (p->Le_t[t] == 0) p->Le_t[t] = p->Le;
+    p->Le = p->Le_t[3];
     // the warm-up: since the fix-up re-runs broken segments in parallel (round 5), a
     // shorter warm-up pays where it is most of a lane's frames (C3: Le 1 408 / 896,
     // C4: 8.5 k); a 60-min track's long segments keep 2 304
@@ -1065,7 +1033,6 @@ int build_plan_host(const amx_chain_desc *desc, const amx_chunk *chunks, int32_t
     b.fs = desc->sample_rate;
     if (desc->env_warm_frames >= 0) p->warm = (desc->env_warm_frames + 127) / 128 * 128;   // whole ring of k_env0 tiles
     if (desc->env_rounds >= 0) p->rounds = desc->env_rounds;
-    if (knobs.env_le_set) p->Le = knobs.env_le;
     if (p->rounds > AMX_ENV_MAX_ROUNDS)
         return b.fail(AMX_EINVAL, "env_rounds %d > %d", desc->env_rounds, AMX_ENV_MAX_ROUNDS);
     p->L = seg_frames > 0 ? seg_frames : 256;

@@ -52,25 +52,14 @@ struct Lti {
     int window_powers(int64_t LS, double tol, int max_k, std::vector<double> &out) const;
 };
 
-// The environment switches of plan construction (measurement and test forms), with
-// their defaults.  from_env() is the only reader of the variables.
+// The two environment switches of plan construction, both for tests, with their
+// defaults.  from_env() is the only reader of the variables.
 struct PlanKnobs {
-    bool env_le_set = false;      // AMX_ENV_LE: the envelope segment length, fixed
-    int env_le = 1024;
-    int up_lout = 480;            // AMX_UP_LOUT: 192 kHz outputs per K segment aimed at
-    bool k192_native = false;     // AMX_K192_NATIVE (set at all): a 192 kHz track takes the native K path
-    int env_guess = 1;            // AMX_ENV_GUESS: k_env0's warm-up start guess
-    int env_wg = 2;               // AMX_ENV_WG: k_env0 waves per CU (<= 0: single-wave workgroups)
-    bool env_lemin_set = false;   // AMX_ENV_LEMIN: the floor of Le; merely set, it is also the
-    int64_t env_lemin = 1024;     //   floor of the tables for 1 and 2 active bands (else 512)
-    bool env_lemin2_set = false;  // AMX_ENV_LEMIN2: the floor of those two tables
-    int64_t env_lemin2 = 512;
-    int env_bandtab = 1;          // AMX_ENV_BANDTAB: 0 keeps the 3-band table for every count
     int up_poly = 1;              // AMX_UP_POLY: 0 turns k_up_poly off
     int f1 = AMX_F1_SPLIT;        // AMX_F1: 2 (AMX_F1_FULL) forces the full-table pass-1 form
     static PlanKnobs from_env();
     // the envelope sizing reads the device's CU count (build_plan_host's ncu)
-    bool needs_ncu(bool multiband_on) const { return multiband_on && env_wg > 0 && !env_le_set; }
+    static bool needs_ncu(bool multiband_on) { return multiband_on; }
 };
 
 // Every host-side field of a plan.  amx_plan (amx_plan.hpp) derives from it and adds the

@@ -9,9 +9,7 @@
 #define AMX_XO_DIM 8      // crossover: 2 low-pass + 2 high-pass SOS sections
 #define AMX_KW_DIM 4      // K-weighting 4th-order DF-II state (v1..v4)
 #define AMX_TF_FRAMES 16  // LDS tile frames (AMX_TF in amx_dev.hpp)
-#ifndef AMX_SCAN_S
 #define AMX_SCAN_S 16     // segments per scan block
-#endif
 #define AMX_ENV_MAX_ROUNDS 16  // envelope fix-up flag words (k_env0 clears them)
 #define AMX_ENV_NCTR 4         // fix-up diagnostic counters per round (after the flags; k_envchain)
 #define AMX_ENV_BACT (AMX_ENV_MAX_ROUNDS * (1 + AMX_ENV_NCTR))  // band-activity words after the counters

@@ -24,8 +24,7 @@
 
 namespace ph {
 
-const char *const KNOBS[] = {"AMX_ENV_LE",    "AMX_UP_LOUT",    "AMX_K192_NATIVE", "AMX_ENV_GUESS", "AMX_ENV_WG",
-                             "AMX_ENV_LEMIN", "AMX_ENV_LEMIN2", "AMX_ENV_BANDTAB", "AMX_UP_POLY",   "AMX_F1"};
+const char *const KNOBS[] = {"AMX_UP_POLY", "AMX_F1"};
 
 struct Case {
     std::string name;
@@ -145,16 +144,6 @@ std::vector<Case> cases() {
     add("mb_ncu_fallback", desc_eq(44100, 1), big).ncu = 2;       // < 3: the 256 fallback
     add("mb_ncu_error", desc_eq(44100, 1), big).ncu = -1;         // the query fails: 256
     {
-        const char *const envs[][2] = {{"AMX_ENV_WG", "0"},      {"AMX_ENV_WG", "7"},        {"AMX_ENV_LE", "2048"},
-                                       {"AMX_ENV_LE", "100"},    {"AMX_ENV_BANDTAB", "0"},   {"AMX_ENV_LEMIN", "1536"},
-                                       {"AMX_ENV_LEMIN", "512"}, {"AMX_ENV_LEMIN2", "256"},  {"AMX_ENV_GUESS", "0"}};
-        for (const auto &e : envs) {
-            Case &c = add(std::string("mb_ncu4_") + e[0] + "=" + e[1], desc_eq(44100, 1), big);
-            c.ncu = 4;
-            c.env.push_back({e[0], e[1]});
-        }
-    }
-    {
         amx_chain_desc d = desc_eq(48000, 1);
         d.env_warm_frames = 1000;
         d.env_rounds = 5;
@@ -202,8 +191,7 @@ std::vector<Case> cases() {
     add("ch_zero_len", desc_eq(48000, 1), chunks({{0, 0, 3000}, {0, 3000, 0}, {1, 3000, 700}}));
     add("ch_one_frame", desc_eq(44100, 1), chunks({{0, 0, 1}}));
     add("ch_L-1_L_L+1", desc_eq(48000), chunks({{0, 0, 255}, {0, 255, 256}, {0, 511, 257}}));
-    add("ch_whole_segments", desc_eq(192000), chunks({{0, 0, 1024}, {0, 1024, 999}, {1, 2023, 512}})).env.push_back(
-        {"AMX_K192_NATIVE", "1"});
+    add("ch_whole_segments", desc_eq(192000), chunks({{0, 0, 1024}, {0, 1024, 999}, {1, 2023, 512}}));
     add("ch_odd_offset", desc_f32(48000, 0, g_lut), chunks({{0, 0, 3001}, {0, 3001, 2000}}));
     add("ch_short", desc_f32(48000, 0, g_lut), chunks({{0, 0, 3}, {0, 4, 2000}}));
     add("ch_empty_track", desc_eq(44100, 1), chunks({{0, 0, 3000}, {2, 3000, 2501}}));
@@ -225,9 +213,6 @@ std::vector<Case> cases() {
     // knobs
     add("AMX_UP_POLY=0", desc_eq(44100), TWO).env.push_back({"AMX_UP_POLY", "0"});
     add("AMX_UP_POLY=1", desc_eq(44100), TWO).env.push_back({"AMX_UP_POLY", "1"});
-    add("AMX_K192_NATIVE=1", desc_eq(192000), TWO).env.push_back({"AMX_K192_NATIVE", "1"});
-    add("AMX_UP_LOUT=96", desc_eq(48000), TWO).env.push_back({"AMX_UP_LOUT", "96"});
-    add("AMX_UP_LOUT=1", desc_eq(44100), TWO).env.push_back({"AMX_UP_LOUT", "1"});
     // every fail exit
     add("err_null_desc", desc(48000), TWO).null_desc = true;
     add("err_null_out", desc(48000), TWO).null_out = true;

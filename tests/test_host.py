@@ -265,3 +265,27 @@ def test_pipelined_slots_keep_every_exchange_tensor():
     assert names, "no attributes found"
     missing = names - set(ShardedTrack._SLOT_KEYS)
     assert not missing, "exchange tensors not kept per slot: %s" % sorted(missing)
+
+
+def test_switch_inventory():
+    """The AMX_* switches the sources read are the eight DESIGN.md §3 lists, and no
+    preprocessor conditional in csrc/ names an AMX_ macro but the guards of AMX_PCM_U8 and
+    AMX_SRC_HASH: a measurement fork or tuning override that comes back shows up here."""
+    import re
+    pkg = os.path.join(ROOT, "audio-mastering-engine_amd")
+    env, cond = set(), set()
+    for d, _, files in os.walk(pkg):
+        for f in files:
+            if not f.endswith((".hip", ".hpp", ".cpp", ".h", ".py")):
+                continue
+            with open(os.path.join(d, f)) as fh:
+                text = fh.read()
+            env |= set(re.findall(r"getenv\(\s*\"(AMX_\w+)\"", text))
+            env |= set(re.findall(r"environ(?:\.get\(|\[)\s*\"(AMX_\w+)\"", text))
+            if os.path.basename(d) == "csrc":
+                for line in re.findall(r"^[ \t]*#[ \t]*(?:if|ifdef|ifndef|elif)\b.*$", text, re.M):
+                    if "AMX_" in line:
+                        cond.add((f, " ".join(line.split("//")[0].split())))
+    assert env == {"AMX_F1", "AMX_UP_POLY", "AMX_LN_SEG", "AMX_LN_WARM", "AMX_LP_FILL", "AMX_LN_MEASURED_BOUND",
+                   "AMX_WAIT_TIMEOUT_S", "AMX_LIB"}
+    assert cond == {("amx_internal.hpp", "#ifndef AMX_PCM_U8"), ("amx_plan.cpp", "#ifndef AMX_SRC_HASH")}
