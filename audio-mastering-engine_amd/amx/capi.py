@@ -14,6 +14,7 @@ c_double_p = ctypes.POINTER(ctypes.c_double)
 c_float_p = ctypes.POINTER(ctypes.c_float)
 
 AMX_OK, AMX_EINVAL, AMX_EHIP, AMX_ENOMEM, AMX_ERANGE = 0, -1, -2, -3, -4
+AMX_EUNSUPPORTED = -5     # FLAC input the device decoder leaves to the host decoder
 ABI_VERSION = 6
 CTL_FAST = 1
 MODES = ("off", "skip", "linear", "dynamic")
@@ -92,6 +93,19 @@ class FlacInfo(ctypes.Structure):
                 ("total_frames", ctypes.c_int64)]
 
 
+class FlacCand(ctypes.Structure):
+    _fields_ = [("offset", ctypes.c_int64), ("limit", ctypes.c_int64), ("slot", ctypes.c_int64),
+                ("block", ctypes.c_int32), ("bps", ctypes.c_int32), ("assign", ctypes.c_int32),
+                ("data_byte", ctypes.c_int32)]
+
+
+class FlacScan(ctypes.Structure):
+    _fields_ = [("n_cand", ctypes.c_int64), ("total_frames", ctypes.c_int64), ("first_frame", ctypes.c_int64),
+                ("scratch_samples", ctypes.c_int64), ("workspace_bytes", ctypes.c_int64),
+                ("channels", ctypes.c_int32), ("bits_per_sample", ctypes.c_int32),
+                ("sample_rate", ctypes.c_int32), ("max_block", ctypes.c_int32)]
+
+
 class TrackSpan(ctypes.Structure):
     _fields_ = [("out_offset", ctypes.c_int64), ("out_frames", ctypes.c_int64),
                 ("track_frame0", ctypes.c_int64), ("track_frames_total", ctypes.c_int64)]
@@ -110,7 +124,8 @@ EXPORTS = ("amx_abi_version", "amx_last_error", "amx_build_id", "amx_plan_create
            "amx_plan_set_limiter_channels",
            "amx_mc_plan_create", "amx_mc_plan_free", "amx_mc_plan_get_info", "amx_mc_run_chunks",
            "amx_mc_split_pairs", "amx_mc_loudness_combine", "amx_mc_peak_pick", "amx_mc_limiter_out",
-           "amx_flac_encode_size", "amx_flac_encode", "amx_flac_encode_size_ex", "amx_flac_encode_ex")
+           "amx_flac_encode_size", "amx_flac_encode", "amx_flac_encode_size_ex", "amx_flac_encode_ex",
+           "amx_flac_scan", "amx_flac_decode_device")
 PCM_FORMATS = {"u8": 0, "s16": 1, "s24": 2, "s32": 3, "f32": 4, "f64": 5,
                "s8": 6, "s16be": 7, "s24be": 8, "s32be": 9, "f32be": 10, "f64be": 11}
 
@@ -195,6 +210,9 @@ def load(path=None):
         [ctypes.POINTER(ctypes.c_int64)] * 3
     L.amx_flac_encode_ex.argtypes = [vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                      ctypes.c_int32, vp, ctypes.c_int64, vp, vp, vp, vp, ctypes.c_int64, vp]
+    L.amx_flac_scan.argtypes = [vp, ctypes.c_int64, vp, ctypes.c_int64, ctypes.POINTER(FlacScan)]
+    L.amx_flac_decode_device.argtypes = [vp, ctypes.c_int64, vp, ctypes.POINTER(FlacScan), vp, ctypes.c_int64, vp,
+                                         ctypes.c_int64, vp, vp, ctypes.c_int64, vp]
     if L.amx_abi_version() != ABI_VERSION:
         raise AmxError("libamx ABI version mismatch")
     L.amx_build_id.restype = ctypes.c_char_p

@@ -5,6 +5,9 @@ The bitstream is decoded by libamx's host decoder (amx_flac_decode, csrc/amx_fla
 frames decoded on a thread pool) into int32 samples left-justified to 32 bits -- the
 value ffmpeg's FLAC decoder hands on -- so the file reaches the device decode as s32
 PCM (amx_pcm_to_s16: >> 16, what the segment muxer's s16 WAV chunks hold).
+decode_flac_device fills the same array on the device instead (amx_flac_decode_device,
+csrc/amx_flacdec.hip): the host only lists the frame starts (amx_flac_scan) and uploads
+the file's bytes.
 
 The write side encodes on the device (amx_flac_encode, csrc/amx_flacenc.hip): the int16
 master stays where the limiter left it, only the encoded frames cross the bus, and the
@@ -80,6 +83,91 @@ def decode_flac(data, threads=0, with_blocks=False):
     if with_blocks:
         return out, info, blocks[:nb.value].copy()
     return out, info
+
+
+def flac_scan(data, room=None):
+    """amx_flac_scan of FLAC bytes (no ID3 tag in front): (rc, FlacScan, candidate table as a
+    uint8 array of FlacCand records, or None unless rc is AMX_OK).  Host only.  `room`: a
+    uint8 array to build the table in (the caller's pinned staging buffer), else a fresh one."""
+    raw = np.frombuffer(data, np.uint8)
+    L = capi.load()
+    sc = capi.FlacScan()
+    rec = ctypes.sizeof(capi.FlacCand)
+    buf = ctypes.c_void_p(raw.ctypes.data)
+    # most streams hold a frame per few kilobytes: room for one per 256 bytes, else ask again
+    cap = raw.size // 256 + 1024 if room is None else room.size // rec
+    tab = np.empty(cap * rec, np.uint8) if room is None else room
+    rc = L.amx_flac_scan(buf, raw.size, tab.ctypes.data_as(ctypes.c_void_p), cap, ctypes.byref(sc))
+    if rc == capi.AMX_ERANGE:
+        cap = sc.n_cand
+        tab = np.empty(cap * rec, np.uint8)
+        rc = L.amx_flac_scan(buf, raw.size, tab.ctypes.data_as(ctypes.c_void_p), cap, ctypes.byref(sc))
+    if rc != capi.AMX_OK:
+        return rc, sc, None
+    return rc, sc, tab[:sc.n_cand * rec]
+
+
+def _flac_host_to_device(data):
+    """decode_flac_device's result by the host decoder and an upload: what a stream outside
+    the device path's range gets (amx.h, AMX_EUNSUPPORTED)"""
+    import torch
+    x, info, blocks = decode_flac(data, with_blocks=True)
+    return torch.from_numpy(x).to("cuda"), info, blocks
+
+
+def decode_flac_device(data):
+    """decode_flac(data, with_blocks=True) on the device: (int32 device tensor [frames,
+    channels] left-justified to 32 bits, FlacInfo, block sizes).  The file's bytes and the
+    host scan's candidate table go up from one pinned buffer; three kernels decode, chain
+    and place the frames (amx_flac_decode_device).  Raises AmxError with
+    decode_flac's messages; a stream the device path does not cover (more than 24 bits, no
+    length in STREAMINFO) goes through decode_flac and an upload."""
+    import torch
+    raw = np.frombuffer(data, np.uint8)
+    o = _skip_id3(raw[:10].tobytes())
+    size = raw.size - o
+    if size <= 0:
+        raise capi.AmxError("not a FLAC stream (empty)")
+    raw = raw[o:]
+    L = capi.load()
+    info = capi.FlacInfo()
+    rc = L.amx_flac_info(ctypes.c_void_p(raw.ctypes.data), size, ctypes.byref(info))
+    if rc != capi.AMX_OK:
+        raise capi.AmxError("not a FLAC stream (amx_flac_info %d)" % rc)
+    # one pinned staging buffer: the stream, then (16-byte aligned) the candidate table
+    rec = ctypes.sizeof(capi.FlacCand)
+    t_off = (size + 15) & ~15
+    stage = torch.empty(t_off + (size // 256 + 1024) * rec, dtype=torch.uint8, pin_memory=True)
+    h = stage.numpy()
+    h[:size] = raw
+    rc, sc, tab = flac_scan(h[:size], room=h[t_off:])
+    if rc == capi.AMX_EUNSUPPORTED:
+        return _flac_host_to_device(data)
+    if rc != capi.AMX_OK:
+        raise capi.AmxError("corrupt FLAC stream (amx_flac_decode %d)" % rc)
+    if tab.ctypes.data != h.ctypes.data + t_off:
+        # more candidates than the staging buffer had room for: a second one for the table
+        stage2 = torch.empty(tab.size, dtype=torch.uint8, pin_memory=True)
+        stage2.numpy()[:] = tab
+        d_data = stage[:size].to("cuda", non_blocking=True)
+        d_cand = stage2.to("cuda", non_blocking=True)
+    else:
+        d_all = stage[:t_off + tab.size].to("cuda", non_blocking=True)
+        d_data, d_cand = d_all[:size], d_all[t_off:]
+    out = torch.empty((sc.total_frames, sc.channels), dtype=torch.int32, device="cuda")
+    d_blocks = torch.empty(sc.n_cand, dtype=torch.int32, device="cuda")
+    d_res = torch.empty(4, dtype=torch.int64, device="cuda")
+    ws = torch.empty((sc.workspace_bytes + 15) // 16 * 2, dtype=torch.int64, device="cuda")
+    capi.check(L.amx_flac_decode_device(capi.ptr(d_data), size, capi.ptr(d_cand), ctypes.byref(sc), capi.ptr(out),
+                                        sc.total_frames, capi.ptr(d_blocks), sc.n_cand, capi.ptr(d_res),
+                                        capi.ptr(ws), ws.numel() * 8, capi.ptr_stream()),
+               "amx_flac_decode_device")
+    res = d_res.cpu().numpy()          # (synchronises: the staging buffers are free again)
+    if res[0] == capi.AMX_EUNSUPPORTED:
+        return _flac_host_to_device(data)
+    if res[0] != capi.AMX_OK or res[1] != sc.total_frames:
+        raise capi.AmxError("corrupt FLAC stream (amx_flac_decode %d)" % res[0])
+    return out, info, d_blocks[:int(res[2])].cpu().numpy()
 
 
 def read_flac_native(path):

@@ -30,6 +30,19 @@ LOUDNORM_TP, LOUDNORM_LRA = -1.5, 11.0      # :229
 ALIMITER = dict(level_in=1.0, level_out=1.0, limit=0.98, attack=5.0, release=50.0)  # :223
 
 
+# optional key flac_decode: where a *.flac input is decoded ("host": amx_flac_decode on a
+# thread pool, the default; "device": amx_flac_decode_device)
+FLAC_DECODE_MODES = ("host", "device")
+
+
+def flac_decode_mode(settings):
+    """the settings' flac_decode ("host" when absent); ValueError for any other value"""
+    mode = (settings or {}).get("flac_decode", "host")
+    if not isinstance(mode, str) or mode not in FLAC_DECODE_MODES:
+        raise ValueError("flac_decode must be one of %s, not %r" % (", ".join(map(repr, FLAC_DECODE_MODES)), mode))
+    return mode
+
+
 def apply_preset(settings, preset_name):
     """mastering_gui.py:165-168: a preset sets the four EQ gains ("None" zeroes them)."""
     s = dict(settings)

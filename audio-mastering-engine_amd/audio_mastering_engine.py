@@ -9,6 +9,9 @@ Mirrors audio_mastering_engine.py's call surface for the hot path:
   ``n+3``, ``n+4``), same ``ValueError`` for missing files, writes a 16-bit WAV -- or,
   for an ``output_file`` named ``*.flac``, a 16-bit FLAC file encoded on the device
   (optional key ``flac_lpc_order`` 0..8: LPC subframes up to that order; absent: 0).
+  The optional key ``flac_decode`` says where a ``*.flac`` input is decoded: ``"host"``
+  (absent: the host decoder and an upload of the decoded samples) or ``"device"`` (the
+  file's bytes go up and are decoded there); any other value is a ``ValueError``.
 * ``process_audio_with_ffmpeg_pipeline`` -- alias of ``master_audio``.
 * ``process_audio(settings, status_cb, progress_cb, art_cb, tag_cb)`` -- the GUI
   wrapper (:94-137): mastering, the optional MP3 export (:97-98, ``export_to_mp3``
@@ -38,7 +41,7 @@ import numpy as np  # noqa: E402
 
 from amx import wavio  # noqa: E402
 from amx.chunking import bounds_for  # noqa: E402
-from amx.settings import EQ_PRESETS  # noqa: E402,F401
+from amx.settings import EQ_PRESETS, flac_decode_mode  # noqa: E402,F401
 
 __all__ = ["master_audio", "process_audio", "process_audio_with_ffmpeg_pipeline", "EQ_PRESETS",
            "master_array", "export_to_mp3"]
@@ -48,18 +51,37 @@ def _noop(*a, **k):
     return None
 
 
-def _device_input(path):
+def _flac_on_device(path):
+    """read_audio_raw's FLAC result with the samples decoded on, and left on, the device:
+    (int32 device tensor [frames, channels], WavInfo of s32 PCM with packet_starts, "s32")"""
+    from amx import flacio
+    with open(path, "rb") as f:
+        x, finfo, blocks = flacio.decode_flac_device(f.read())
+    info = wavio.WavInfo(finfo.sample_rate, finfo.channels, 1, 32)
+    info.packet_starts = np.concatenate([[0], np.cumsum(blocks.astype(np.int64))[:-1]])
+    return x, info, "s32"
+
+
+def _device_input(path, settings=None):
     """The input file on the device, as the chunk chain reads it: (d_in, fs, frames,
     channels_in, input_s16, WavInfo).  float32 stays float32 (the chain's first
     kernel quantises it, A.1); every other format is decoded to stereo s16 by
-    amx_pcm_to_s16 (what ffmpeg's split writes + pydub's set_channels(2))."""
+    amx_pcm_to_s16 (what ffmpeg's split writes + pydub's set_channels(2)).  With the
+    settings key flac_decode = "device" a FLAC file's samples never exist on the host:
+    amx_pcm_to_s16 reads the device decoder's array."""
     import torch
-    from amx import capi
-    raw, info, code = wavio.read_audio_raw(path)          # WAV, AIFF / AIFF-C or FLAC
+    from amx import capi, flacio
+    if flac_decode_mode(settings) == "device" and flacio.is_flac(path):
+        d_raw, info, code = _flac_on_device(path)
+        frames = int(d_raw.shape[0])
+    else:
+        raw, info, code = wavio.read_audio_raw(path)      # WAV, AIFF / AIFF-C or FLAC
+        frames = raw.size // info.block_align
+        d_raw = None
     if not 1 <= info.channels <= 8:
         raise ValueError("1 to 8 channels are supported (%d channels)" % info.channels)
-    frames = raw.size // info.block_align
-    d_raw = torch.from_numpy(raw.copy()).to("cuda")
+    if d_raw is None:
+        d_raw = torch.from_numpy(raw.copy()).to("cuda")
     if code == "f32":
         return d_raw.view(torch.float32), info.sample_rate, frames, info.channels, False, info
     if info.channels > 2:
@@ -120,9 +142,10 @@ def master_audio(settings, status_callback=None, progress_callback=None):
     input_file, output_file = settings.get("input_file"), settings.get("output_file")
     if not input_file or not output_file:
         raise ValueError("Input or output file not specified.")              # :173
+    flac_decode_mode(settings)                         # a bad flac_decode: before any file is read
     status("Splitting audio into manageable chunks...")                       # :176
     progress(0, 100)                                                          # :177
-    d_in, fs, frames, ch_in, s16, info = _device_input(input_file)
+    d_in, fs, frames, ch_in, s16, info = _device_input(input_file, settings)
     bounds = bounds_for(frames, fs, info)                                     # :178
     status("Splitting complete.")                                             # :180
     num_chunks = len(bounds)

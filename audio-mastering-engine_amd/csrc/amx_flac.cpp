@@ -378,6 +378,64 @@ AMX_API int amx_flac_info(const uint8_t *data, int64_t size, amx_flac_info_t *in
     return AMX_OK;
 }
 
+// The candidate table of the device decoder (amx_flacdec.hip): the sync + CRC-8 header
+// scan amx_flac_decode runs, with each candidate's parsed header, read limit and scratch slot
+AMX_API int amx_flac_scan(const uint8_t *data, int64_t size, amx_flac_cand_t *cand, int64_t max_cand,
+                          amx_flac_scan_t *scan) {
+    if (!data || !scan) return AMX_EINVAL;
+    std::memset(scan, 0, sizeof *scan);
+    StreamInfo si;
+    const int rc = parse_streaminfo(data, size, si);
+    if (rc != AMX_OK) return rc;
+    scan->total_frames = si.total;
+    scan->first_frame = si.first_frame;
+    scan->channels = si.channels;
+    scan->bits_per_sample = si.bps;
+    scan->sample_rate = si.rate;
+    // what the device path leaves to the host decoder (include/amx.h)
+    if (si.bps > 24 || si.total <= 0 || si.total > size * 6144) return AMX_EUNSUPPORTED;
+    const int C = si.channels;
+    const int64_t out_samples = si.total * C;
+    int64_t nc = 0, slot = 0;
+    int max_block = 0;
+    int64_t b = si.first_frame;
+    while (b + 1 < size) {
+        const void *hit = std::memchr(data + b, 0xFF, (size_t)(size - 1 - b));
+        if (!hit) break;
+        b = (const uint8_t *)hit - data;
+        FrameHdr h;
+        if ((data[b + 1] & 0xFE) == 0xF8 && parse_header(data, size, b, si, h)) {
+            if (nc == 0 && b != si.first_frame) return AMX_EINVAL;
+            const int64_t stride = ((int64_t)h.block + 15) & ~(int64_t)15;
+            if (cand && nc < max_cand) {
+                amx_flac_cand_t &c = cand[nc];
+                c.offset = b;
+                // a frame is never longer than STREAMINFO's largest frame, or (unknown) than
+                // twice its verbatim size (decode_frame's bound)
+                c.limit = si.max_frame > 0 ? si.max_frame : 2 * ((int64_t)h.block * C * (h.bps + 1) / 8) + 1024;
+                c.slot = slot;
+                c.block = h.block;
+                c.bps = h.bps;
+                c.assign = h.assign;
+                c.data_byte = (int32_t)(h.data_bit / 8 - b);
+            }
+            slot += stride * C;
+            // a table crowded with false syncs: the scratch would dwarf the output
+            if (slot > 4 * out_samples + (int64_t(16) << 20)) return AMX_EUNSUPPORTED;
+            max_block = std::max(max_block, h.block);
+            nc++;
+        }
+        b++;
+    }
+    scan->n_cand = nc;
+    scan->scratch_samples = slot;
+    scan->workspace_bytes = 32 * nc + 64 + 4 * slot;
+    scan->max_block = max_block;
+    if (nc == 0) return AMX_EINVAL;
+    if (!cand || nc > max_cand) return AMX_ERANGE;
+    return AMX_OK;
+}
+
 AMX_API int amx_flac_decode(const uint8_t *data, int64_t size, int32_t *out, int64_t out_frames,
                             int64_t *frames_out, int32_t threads, int32_t *blocks, int64_t max_blocks,
                             int64_t *n_blocks) {

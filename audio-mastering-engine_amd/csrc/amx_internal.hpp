@@ -27,6 +27,8 @@
 #define AMX_PCM_F64BE 11
 #endif
 
+struct amx_flac_cand_t;   // include/amx.h
+
 // ---------------------------------------------------------------- launchers
 namespace amx {
 struct Launch {
@@ -102,6 +104,12 @@ void flac_encode_size(int64_t frames, int C, int B, int lpc_order, int64_t *nf, 
 hipError_t launch_flac_encode(const int16_t *pcm, int64_t frames, int C, int fs, int B, int lpc_order, uint8_t *out,
                               int64_t capacity, uint32_t *frame_bytes, uint32_t *sub_bits, int64_t *total,
                               void *ws, hipStream_t st);
+// FLAC input on the device (amx_flacdec.hip): the workspace of, and the three kernels
+// behind, amx_flac_decode_device (cand: the device copy of amx_flac_scan's table)
+int64_t flac_decode_ws_bytes(int64_t n_cand, int64_t scratch_samples);
+hipError_t launch_flac_decode(const uint8_t *data, int64_t size, const ::amx_flac_cand_t *cand, int64_t nc,
+                              int C, int64_t total, int64_t first_frame, int64_t scratch_samples, int32_t *out,
+                              int32_t *blocks, int64_t max_blocks, int64_t *result, void *ws, hipStream_t st);
 hipError_t launch_env(const DynLaunch &d, const uint16_t *m, double *ck, double *sv, double *ev,
                       int *act, int *list, int *hmark, int *prev, int *list0, int *flags, int rounds,
                       int part);

@@ -820,6 +820,33 @@ int amx_flac_encode_ex(const int16_t *d_pcm, int64_t frames, int32_t channels, i
     return AMX_OK;
 }
 
+int amx_flac_decode_device(const uint8_t *d_data, int64_t size, const amx_flac_cand_t *d_cand,
+                           const amx_flac_scan_t *scan, int32_t *d_out, int64_t out_frames, int32_t *d_blocks,
+                           int64_t max_blocks, int64_t *d_result, void *d_workspace, int64_t workspace_bytes,
+                           void *stream) {
+    if (!d_data || !d_cand || !scan || !d_out || !d_blocks || !d_result || !d_workspace)
+        return fail(AMX_EINVAL, "null argument");
+    if (size < 42 || scan->n_cand < 1 || scan->n_cand > INT32_MAX || scan->channels < 1 || scan->channels > 8 ||
+        scan->total_frames < 1 || scan->scratch_samples < 0 || scan->first_frame < 42 || scan->first_frame >= size ||
+        scan->bits_per_sample < 4 || scan->bits_per_sample > 24)
+        return fail(AMX_EINVAL, "not a scan amx_flac_scan accepted");
+    if (reinterpret_cast<uintptr_t>(d_workspace) & 15) return fail(AMX_EINVAL, "workspace must be 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(d_out) & 3 || reinterpret_cast<uintptr_t>(d_blocks) & 3 ||
+        reinterpret_cast<uintptr_t>(d_result) & 7 || reinterpret_cast<uintptr_t>(d_cand) & 7)
+        return fail(AMX_EINVAL, "misaligned argument");
+    if (out_frames < scan->total_frames)
+        return fail(AMX_ERANGE, "out_frames %lld < %lld", (long long)out_frames, (long long)scan->total_frames);
+    if (max_blocks < 1) return fail(AMX_ERANGE, "max_blocks %lld < 1", (long long)max_blocks);
+    const int64_t need = amx::flac_decode_ws_bytes(scan->n_cand, scan->scratch_samples);
+    if (workspace_bytes < need)
+        return fail(AMX_ERANGE, "workspace_bytes %lld < %lld (amx_flac_scan)", (long long)workspace_bytes,
+                    (long long)need);
+    HIPCHK(amx::launch_flac_decode(d_data, size, d_cand, scan->n_cand, scan->channels, scan->total_frames,
+                                   scan->first_frame, scan->scratch_samples, d_out, d_blocks, max_blocks, d_result,
+                                   d_workspace, (hipStream_t)stream));
+    return AMX_OK;
+}
+
 int amx_plan_set_gate(amx_plan *p, const int32_t *d_gate) {
     if (!p) return fail(AMX_EINVAL, "null plan");
     p->gate = d_gate;

@@ -42,6 +42,7 @@ extern "C" {
 #define AMX_EHIP -2       /* HIP runtime error */
 #define AMX_ENOMEM -3     /* host allocation failed */
 #define AMX_ERANGE -4     /* a size or filter is outside what the plan supports */
+#define AMX_EUNSUPPORTED -5   /* FLAC input: a stream the device decoder leaves to the host decoder */
 
 /* ABI history.  3 -> 4 (round 6): amx_loudnorm_desc gained reuse_stream (the struct
  * grew), amx_ln_shard.pad_ became `windowed`, d_edge went from [2][16][2] to [2][80][2]
@@ -51,7 +52,9 @@ extern "C" {
  * of an existing structure changed.
  * 5 -> 6: amx_flac_encode_size_ex and amx_flac_encode_ex added (lpc_order: LPC subframes
  * of order 1..8 in the FLAC output); the two older entry points are the _ex forms with
- * lpc_order 0 and give the same sizes and bytes as before. */
+ * lpc_order 0 and give the same sizes and bytes as before.
+ * 6 (unchanged): amx_flac_scan and amx_flac_decode_device added (FLAC input decoded on the
+ * device) with their two structures and AMX_EUNSUPPORTED; nothing that existed changed. */
 #define AMX_ABI_VERSION 6
 
 #if defined(__GNUC__)
@@ -247,6 +250,63 @@ AMX_API int amx_flac_info(const uint8_t *data, int64_t size, amx_flac_info_t *in
 AMX_API int amx_flac_decode(const uint8_t *data, int64_t size, int32_t *out, int64_t out_frames,
                             int64_t *frames_out, int32_t threads, int32_t *blocks, int64_t max_blocks,
                             int64_t *n_blocks);
+
+/* FLAC input decoded on the device.  The file's bytes go to the device as
+ * they are; amx_flac_scan (host only, no HIP call) lists every frame-start candidate --
+ * each sync code whose header parses with a matching CRC-8, as amx_flac_decode finds them
+ * -- with the parsed header, the read limit and a slot in the scratch array;
+ * amx_flac_decode_device decodes every candidate (one work item each), chains the frames
+ * that tile the stream from the first one and writes d_out int32 [total_frames][channels],
+ * byte for byte the array amx_flac_decode fills, and d_blocks, its block list.
+ *
+ * Streams: STREAMINFO depths 4..24, 1..8 channels, a known length.  amx_flac_scan returns
+ * AMX_EUNSUPPORTED -- take amx_flac_decode -- for a depth above 24, a STREAMINFO length of
+ * 0 or one beyond 6144 samples per file byte, and for a candidate table whose scratch
+ * would pass 4 x the output + 64 MiB (a file crowded with false syncs).  A frame header
+ * that codes more than 24 bits inside a supported stream gives the same value as the
+ * status word (below) when the chain reaches it.
+ * Widths: samples, warm-ups and residuals are int32; FIXED predictors wrap in 32 bits; the
+ * LPC sum is a wrapping 64-bit accumulate with an arithmetic shift.  A reconstructed
+ * sample that does not fit its subframe's effective width (depth, + 1 for a side channel,
+ * - wasted bits), or a residual that does not fit int32, makes the candidate not ok,
+ * exactly like a failed CRC-16.  RFC 9639 calls such streams invalid; amx_flac_decode
+ * decodes them in wrapping int64.  So on invalid streams the device path is the stricter
+ * one (AMX_EINVAL where the host may hand on samples); on valid streams the two are
+ * identical.
+ *
+ * amx_flac_scan: cand NULL or max_cand too small: scan->n_cand is still the count and the
+ * call returns AMX_ERANGE (call again with room).  Errors: AMX_EINVAL (not FLAC; no frame,
+ * or the first candidate is not the first frame: amx_flac_decode's outcome).
+ * amx_flac_decode_device: d_data the file's bytes (`size` of them, from "fLaC"), d_cand the
+ * device copy of the table, scan the host structure amx_flac_scan filled, d_out room for
+ * out_frames >= scan->total_frames frames, d_blocks room for max_blocks >= 1 block sizes
+ * (scan->n_cand always suffices), d_workspace 16-byte aligned with workspace_bytes >=
+ * scan->workspace_bytes (= 32 n_cand + 64 + 4 scratch_samples).  Arguments are validated
+ * before the first launch; kernels only, no host synchronisation.  After the caller's own
+ * synchronise d_result int64 [4] holds: [0] AMX_OK, AMX_EINVAL (a corrupt or missing frame:
+ * the chain ends before STREAMINFO's length), AMX_ERANGE (max_blocks too small) or
+ * AMX_EUNSUPPORTED; [1] the frames written (scan->total_frames; 0 unless AMX_OK); [2] the
+ * chained FLAC frames, d_blocks[0 .. [2]) their block sizes; [3] the candidate the chain
+ * stopped at (-1: a clean end).  Unless [0] is AMX_OK, d_out is not written. */
+typedef struct amx_flac_cand_t {
+    int64_t offset;      /* byte offset of the sync code */
+    int64_t limit;       /* reads stop at min(size, offset + limit) */
+    int64_t slot;        /* first sample of the candidate's scratch slot (a multiple of 16) */
+    int32_t block;       /* samples per channel, 1..65535 */
+    int32_t bps;         /* the frame's sample depth */
+    int32_t assign;      /* channel assignment 0..10 */
+    int32_t data_byte;   /* header length with its CRC-8: the first subframe starts there */
+} amx_flac_cand_t;
+typedef struct amx_flac_scan_t {
+    int64_t n_cand, total_frames, first_frame, scratch_samples, workspace_bytes;
+    int32_t channels, bits_per_sample, sample_rate, max_block;   /* max_block: the largest candidate's */
+} amx_flac_scan_t;
+AMX_API int amx_flac_scan(const uint8_t *data, int64_t size, amx_flac_cand_t *cand, int64_t max_cand,
+                          amx_flac_scan_t *scan);
+AMX_API int amx_flac_decode_device(const uint8_t *d_data, int64_t size, const amx_flac_cand_t *d_cand,
+                                   const amx_flac_scan_t *scan, int32_t *d_out, int64_t out_frames,
+                                   int32_t *d_blocks, int64_t max_blocks, int64_t *d_result, void *d_workspace,
+                                   int64_t workspace_bytes, void *stream);
 
 /* (ABI 5) FLAC output (:223 writes output_file with the container its extension names;
  * a .flac master).  The encoder runs on the device: d_pcm int16 [frames][channels]
