@@ -125,7 +125,8 @@ EXPORTS = ("amx_abi_version", "amx_last_error", "amx_build_id", "amx_plan_create
            "amx_mc_plan_create", "amx_mc_plan_free", "amx_mc_plan_get_info", "amx_mc_run_chunks",
            "amx_mc_split_pairs", "amx_mc_loudness_combine", "amx_mc_peak_pick", "amx_mc_limiter_out",
            "amx_flac_encode_size", "amx_flac_encode", "amx_flac_encode_size_ex", "amx_flac_encode_ex",
-           "amx_flac_scan", "amx_flac_decode_device")
+           "amx_flac_scan", "amx_flac_decode_device",
+           "amx_resample_size", "amx_resampler_create", "amx_resampler_run", "amx_resampler_free")
 PCM_FORMATS = {"u8": 0, "s16": 1, "s24": 2, "s32": 3, "f32": 4, "f64": 5,
                "s8": 6, "s16be": 7, "s24be": 8, "s32be": 9, "f32be": 10, "f64be": 11}
 
@@ -213,6 +214,12 @@ def load(path=None):
     L.amx_flac_scan.argtypes = [vp, ctypes.c_int64, vp, ctypes.c_int64, ctypes.POINTER(FlacScan)]
     L.amx_flac_decode_device.argtypes = [vp, ctypes.c_int64, vp, ctypes.POINTER(FlacScan), vp, ctypes.c_int64, vp,
                                          ctypes.c_int64, vp, vp, ctypes.c_int64, vp]
+    L.amx_resample_size.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)] + \
+        [ctypes.POINTER(ctypes.c_int32)] * 3
+    L.amx_resampler_create.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(vp)]
+    L.amx_resampler_run.argtypes = [vp, vp, ctypes.c_int64, vp, ctypes.c_int64, vp]
+    L.amx_resampler_free.argtypes = [vp]
+    L.amx_resampler_free.restype = None
     if L.amx_abi_version() != ABI_VERSION:
         raise AmxError("libamx ABI version mismatch")
     L.amx_build_id.restype = ctypes.c_char_p

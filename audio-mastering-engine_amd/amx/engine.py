@@ -22,7 +22,7 @@ import torch
 
 from . import capi, design, loudness
 from .chunking import plan_tracks, packet_frames
-from .settings import ALIMITER, LOUDNORM_LRA, LOUDNORM_TP
+from .settings import ALIMITER, LOUDNORM_LRA, LOUDNORM_TP, output_rate
 
 
 class DynamicModeUnsupported(NotImplementedError):
@@ -724,14 +724,45 @@ class MultiChannelJob:
         return False
 
 
+def delivery_rate(settings, input_rate, channels):
+    """The settings key output_rate (amx.settings.output_rate) checked against every rate
+    the master of this call can be at: the input's, and 192 kHz when loudnorm may take its
+    dynamic mode (lufs set, at most two channels).  None: deliver the master as it is.
+    ValueError for a bad key, or for a pair amx_resample_size refuses (both rates named)."""
+    from . import resample
+    target = output_rate(settings, input_rate)
+    if target is not None:
+        ends = [int(input_rate)]
+        if (settings or {}).get("lufs") is not None and int(channels) <= 2:
+            ends.append(192000)
+        for fs in ends:
+            resample.check_pair(fs, target)
+    return target
+
+
+def deliver(y, report, target):
+    """The finished master y (report["sample_rate"] its rate) at the delivery rate: the
+    device resampler after the alimiter (amx/resample.py) when the two differ; the report
+    then carries the delivered rate and resampled_from, the master's."""
+    fs = int(report["sample_rate"])
+    if target is None or target == fs:
+        return y
+    from . import resample
+    report.update(sample_rate=int(target), resampled_from=fs)
+    return resample.resample_s16(y, fs, target)
+
+
 def master_array(x, sample_rate, settings, *, quantum=None, seg_frames=128, limiter_seg_frames=0,
                  limiter_warm_frames=-1):
     """In-memory twin of master_audio: float32 [frames, C] (C = 1/2,
     any device) -> int16 [frames', 2] CUDA tensor (the 16-bit WAV the reference
-    writes) and a report dict."""
+    writes) and a report dict.  report["sample_rate"] is the rate of the returned frames:
+    the input's, 192000 after loudnorm's dynamic mode, or the settings key output_rate's
+    when it names another (report["resampled_from"] then holds the master's)."""
     x = torch.as_tensor(x)
     if x.dim() == 1:
         x = x.reshape(-1, 1)
+    target = delivery_rate(settings, sample_rate, x.shape[1])    # a bad output_rate: before any kernel
     if x.dtype == torch.int16:
         s16 = True
     else:
@@ -745,7 +776,7 @@ def master_array(x, sample_rate, settings, *, quantum=None, seg_frames=128, limi
         y = job.run(x)
         job.fetch_report(raise_dynamic=True)
         job.report.update(sample_rate=job.fs, job=job)
-        return y, job.report
+        return deliver(y, job.report, target), job.report
     job = MasteringJob(sample_rate, x.shape[1], settings, [x.shape[0]], quantum=quantum,
                        input_s16=s16, seg_frames=seg_frames, limiter_seg_frames=limiter_seg_frames,
                        limiter_warm_frames=limiter_warm_frames)
@@ -759,4 +790,4 @@ def master_array(x, sample_rate, settings, *, quantum=None, seg_frames=128, limi
     else:
         job.report["sample_rate"] = job.fs
     job.report["job"] = job
-    return y, job.report
+    return deliver(y, job.report, target), job.report

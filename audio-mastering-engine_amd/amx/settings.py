@@ -43,6 +43,20 @@ def flac_decode_mode(settings):
     return mode
 
 
+def output_rate(settings, input_rate):
+    """the sample rate the master is delivered at, from the optional settings key
+    output_rate: None (absent or None: the master's own rate, no conversion), a positive int
+    (Hz) or "input" (input_rate).  ValueError for anything else; bool is not a rate."""
+    rate = (settings or {}).get("output_rate")
+    if rate is None:
+        return None
+    if isinstance(rate, str) and rate == "input":
+        return int(input_rate)
+    if isinstance(rate, int) and not isinstance(rate, bool) and rate > 0:
+        return rate
+    raise ValueError("output_rate must be a positive int (Hz), \"input\" or None, not %r" % (rate,))
+
+
 def apply_preset(settings, preset_name):
     """mastering_gui.py:165-168: a preset sets the four EQ gains ("None" zeroes them)."""
     s = dict(settings)

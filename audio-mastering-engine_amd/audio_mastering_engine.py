@@ -41,7 +41,7 @@ import numpy as np  # noqa: E402
 
 from amx import wavio  # noqa: E402
 from amx.chunking import bounds_for  # noqa: E402
-from amx.settings import EQ_PRESETS, flac_decode_mode  # noqa: E402,F401
+from amx.settings import EQ_PRESETS, flac_decode_mode, output_rate  # noqa: E402,F401
 
 __all__ = ["master_audio", "process_audio", "process_audio_with_ffmpeg_pipeline", "EQ_PRESETS",
            "master_array", "export_to_mp3"]
@@ -62,10 +62,12 @@ def _flac_on_device(path):
     return x, info, "s32"
 
 
-def _device_input(path, settings=None):
+def _device_input(path, settings=None, on_info=None):
     """The input file on the device, as the chunk chain reads it: (d_in, fs, frames,
-    channels_in, input_s16, WavInfo).  float32 stays float32 (the chain's first
-    kernel quantises it, A.1); every other format is decoded to stereo s16 by
+    channels_in, input_s16, WavInfo).  on_info(sample_rate, channels) is called once the
+    header is known, before the samples go to the device or a conversion kernel runs (a
+    FLAC file decoded on the device: after its decode).  float32 stays float32 (the chain's
+    first kernel quantises it, A.1); every other format is decoded to stereo s16 by
     amx_pcm_to_s16 (what ffmpeg's split writes + pydub's set_channels(2)).  With the
     settings key flac_decode = "device" a FLAC file's samples never exist on the host:
     amx_pcm_to_s16 reads the device decoder's array."""
@@ -80,6 +82,8 @@ def _device_input(path, settings=None):
         d_raw = None
     if not 1 <= info.channels <= 8:
         raise ValueError("1 to 8 channels are supported (%d channels)" % info.channels)
+    if on_info is not None:
+        on_info(info.sample_rate, info.channels)
     if d_raw is None:
         d_raw = torch.from_numpy(raw.copy()).to("cuda")
     if code == "f32":
@@ -143,16 +147,21 @@ def master_audio(settings, status_callback=None, progress_callback=None):
     if not input_file or not output_file:
         raise ValueError("Input or output file not specified.")              # :173
     flac_decode_mode(settings)                         # a bad flac_decode: before any file is read
+    output_rate(settings, 0)                           # a bad output_rate likewise
+    from amx.engine import delivery_rate, deliver
+    # a master rate the resampler cannot take to output_rate: before any kernel runs
+    check = lambda rate, channels: delivery_rate(settings, rate, channels)   # noqa: E731
     status("Splitting audio into manageable chunks...")                       # :176
     progress(0, 100)                                                          # :177
-    d_in, fs, frames, ch_in, s16, info = _device_input(input_file, settings)
+    d_in, fs, frames, ch_in, s16, info = _device_input(input_file, settings, check)
+    target = output_rate(settings, fs)
     bounds = bounds_for(frames, fs, info)                                     # :178
     status("Splitting complete.")                                             # :180
     num_chunks = len(bounds)
     total_steps = num_chunks + 4                                              # :184
     if ch_in > 2:
         return _master_multichannel(settings, status, progress, d_in, fs, frames, ch_in, s16, bounds,
-                                    output_file)
+                                    output_file, target)
     job = MasteringJob(fs, ch_in, settings, [frames], input_s16=s16,
                        chunks=[(0, s, n) for s, n in bounds])
     # every chunk's chain runs in the same launches (chunks are independent,
@@ -195,19 +204,23 @@ def master_audio(settings, status_callback=None, progress_callback=None):
     else:
         # the alimiter ran on the 192 kHz file inside dynamic_track (:223 keeps its rate)
         y, out_fs = dyn[0], dyn[1]["sample_rate"]
-    _write_output(output_file, y, out_fs, settings)
+    rate = {"sample_rate": out_fs}
+    y = deliver(y, rate, target)                       # output_rate: the resampler after the alimiter
+    _write_output(output_file, y, rate["sample_rate"], settings)
     progress(total_steps, total_steps)                                        # :224
     logging.info(f"Finished GPU pipeline, exported to {output_file}")
     return output_file
 
 
-def _master_multichannel(settings, status, progress, d_in, fs, frames, channels, s16, bounds, output_file):
+def _master_multichannel(settings, status, progress, d_in, fs, frames, channels, s16, bounds, output_file,
+                         target=None):
     """master_audio for a file with 3..8 channels: the chain over the interleaved stream
     (:252), the measurement over the C channels and the C-channel alimiter
     (amx.engine.MultiChannelJob), with the same status strings and progress sequence.
-    Loudnorm's dynamic mode is not run for such a file (DynamicModeUnsupported)."""
+    Loudnorm's dynamic mode is not run for such a file (DynamicModeUnsupported).  target:
+    the delivery rate (settings key output_rate), None: the file's own."""
     import torch
-    from amx.engine import MultiChannelJob
+    from amx.engine import MultiChannelJob, deliver
     num_chunks = len(bounds)
     total_steps = num_chunks + 4
     job = MultiChannelJob(fs, channels, settings, frames, input_s16=s16, chunks=[(0, s, n) for s, n in bounds])
@@ -231,7 +244,9 @@ def _master_multichannel(settings, status, progress, d_in, fs, frames, channels,
         job.measure(lufs_on=False)
     status("Applying final limiting and exporting...")                        # :221
     progress(num_chunks + 3, total_steps)                                     # :222
-    _write_output(output_file, job.finalize(), fs, settings)
+    rate = {"sample_rate": fs}
+    y = deliver(job.finalize(), rate, target)
+    _write_output(output_file, y, rate["sample_rate"], settings)
     progress(total_steps, total_steps)                                        # :224
     logging.info(f"Finished GPU pipeline, exported to {output_file}")
     job.close()

@@ -110,6 +110,12 @@ int64_t flac_decode_ws_bytes(int64_t n_cand, int64_t scratch_samples);
 hipError_t launch_flac_decode(const uint8_t *data, int64_t size, const ::amx_flac_cand_t *cand, int64_t nc,
                               int C, int64_t total, int64_t first_frame, int64_t scratch_samples, int32_t *out,
                               int32_t *blocks, int64_t max_blocks, int64_t *result, void *ws, hipStream_t st);
+// the output resampler (amx_resample.hip): bank = the one row when L == 1, else the bank
+// tap-major [alloc][L]; resample_prepare raises the kernels' dynamic-LDS limits where the
+// pair's launches pass 64 KiB (hipErrorInvalidValue: a window larger than they take)
+hipError_t resample_prepare(int L, int M, int alloc, int C);
+hipError_t launch_resample(int L, int M, int alloc, int center, int C, const float *bank, int ncu,
+                           const int16_t *in, int64_t frames, int16_t *out, int64_t out_frames, hipStream_t st);
 hipError_t launch_env(const DynLaunch &d, const uint16_t *m, double *ck, double *sv, double *ev,
                       int *act, int *list, int *hmark, int *prev, int *list0, int *flags, int rounds,
                       int part);

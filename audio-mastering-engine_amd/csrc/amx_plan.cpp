@@ -1324,3 +1324,105 @@ int amx_mc_limiter_out(const amx_plan *p, const amx_final_desc *fd, const int16_
 }
 
 }  // extern "C"
+
+// ==================================================================================
+// The output resampler (amx_resample.hip): the finished master at the
+// rate the caller asks for.  Replaces no reference line (the reference writes the master
+// at the rate the last filter leaves it, :223); it is the `-ar R` of a loudnorm recipe.
+struct amx_resampler {
+    int32_t in_rate = 0, out_rate = 0, channels = 0;
+    int32_t L = 1, M = 1, taps = 0, alloc = 0, phases = 0;
+    int32_t ncu = 1;           // the device's CUs (the persistent form's grid)
+    float *d_bank = nullptr;
+};
+
+namespace {
+// the pair's geometry, or the error: phases = L (no output interpolates)
+int resample_geometry(int32_t in_rate, int32_t out_rate, int *L, int *M, int *taps, int *alloc) {
+    if (in_rate <= 0 || out_rate <= 0) return fail(AMX_EINVAL, "rates must be positive (%d -> %d)", in_rate, out_rate);
+    if (in_rate == out_rate) return fail(AMX_EINVAL, "equal rates (%d): nothing to resample", in_rate);
+    amx::swr_geometry(in_rate, out_rate, L, M);
+    if (*L > 1024 || amx::swr_phases(in_rate, out_rate, AMX_RS_MAX_ALLOC) < 0 ||
+        amx::swr_filter(in_rate, out_rate, taps, alloc, nullptr, AMX_RS_MAX_ALLOC))
+        return fail(AMX_ERANGE, "%d -> %d Hz is outside the resampler's pairs (%d phases; at most 1024, filter rows "
+                    "of at most %d taps)", in_rate, out_rate, *L, AMX_RS_MAX_ALLOC);
+    return AMX_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int amx_resample_size(int32_t in_rate, int32_t out_rate, int64_t frames, int64_t *out_frames, int32_t *taps,
+                      int32_t *alloc, int32_t *phases) {
+    if (frames < 0) return fail(AMX_EINVAL, "frames must be >= 0");
+    int L = 1, M = 1, t = 0, al = 0;
+    if (int rc = resample_geometry(in_rate, out_rate, &L, &M, &t, &al)) return rc;
+    if (frames > (INT64_MAX - M) / L) return fail(AMX_ERANGE, "%lld frames", (long long)frames);
+    if (out_frames) *out_frames = (frames * L + M - 1) / M;
+    if (taps) *taps = t;
+    if (alloc) *alloc = al;
+    if (phases) *phases = L;
+    return AMX_OK;
+}
+
+void amx_resampler_free(amx_resampler *h) {
+    if (!h) return;
+    if (h->d_bank) (void)hipFree(h->d_bank);
+    delete h;
+}
+
+int amx_resampler_create(int32_t in_rate, int32_t out_rate, int32_t channels, amx_resampler **out) {
+    if (!out) return fail(AMX_EINVAL, "null argument");
+    *out = nullptr;
+    if (channels < 1 || channels > 8) return fail(AMX_EINVAL, "channels must be 1..8");
+    std::unique_ptr<amx_resampler, void (*)(amx_resampler *)> h(new (std::nothrow) amx_resampler, amx_resampler_free);
+    if (!h) return fail(AMX_ENOMEM, "out of host memory");
+    int L = 1, M = 1, t = 0, al = 0;
+    if (int rc = resample_geometry(in_rate, out_rate, &L, &M, &t, &al)) return rc;
+    h->in_rate = in_rate;
+    h->out_rate = out_rate;
+    h->channels = channels;
+    h->L = L;
+    h->M = M;
+    h->taps = t;
+    h->alloc = al;
+    h->phases = L;
+    std::vector<float> bank((size_t)L * al), dev;
+    if (amx::swr_bank(in_rate, out_rate, bank.data(), AMX_RS_MAX_ALLOC)) return fail(AMX_ERANGE, "no filter bank");
+    if (L == 1) {
+        dev = bank;
+    } else {
+        // tap-major: the lanes of a wave read one tap of their own rows
+        dev.resize(bank.size());
+        for (int ph = 0; ph < L; ph++)
+            for (int i = 0; i < al; i++) dev[(size_t)i * L + ph] = bank[(size_t)ph * al + i];
+    }
+    int device = 0, ncu = 0;
+    HIPCHK(hipGetDevice(&device));
+    HIPCHK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device));
+    h->ncu = ncu > 0 ? ncu : 1;
+    HIPCHK(amx::resample_prepare(L, M, al, channels));
+    HIPCHK(hipMalloc((void **)&h->d_bank, dev.size() * sizeof(float)));
+    HIPCHK(hipMemcpy(h->d_bank, dev.data(), dev.size() * sizeof(float), hipMemcpyHostToDevice));
+    *out = h.release();
+    return AMX_OK;
+}
+
+int amx_resampler_run(const amx_resampler *h, const int16_t *d_in, int64_t frames, int16_t *d_out,
+                      int64_t out_capacity_frames, void *stream) {
+    if (!h) return fail(AMX_EINVAL, "null resampler");
+    if (frames < 0) return fail(AMX_EINVAL, "frames must be >= 0");
+    if (frames == 0) return AMX_OK;
+    if (!d_in || !d_out) return fail(AMX_EINVAL, "null argument");
+    if (frames > (INT64_MAX - h->M) / h->L) return fail(AMX_EINVAL, "%lld frames", (long long)frames);
+    const int64_t n_out = (frames * h->L + h->M - 1) / h->M;
+    if (out_capacity_frames < n_out)
+        return fail(AMX_EINVAL, "out_capacity_frames %lld < %lld (amx_resample_size)", (long long)out_capacity_frames,
+                    (long long)n_out);
+    if ((n_out + AMX_RS_TILE - 1) / AMX_RS_TILE > INT32_MAX) return fail(AMX_EINVAL, "%lld frames", (long long)frames);
+    HIPCHK(amx::launch_resample(h->L, h->M, h->alloc, (h->taps - 1) / 2, h->channels, h->d_bank, h->ncu, d_in, frames,
+                                d_out, n_out, (hipStream_t)stream));
+    return AMX_OK;
+}
+
+}  // extern "C"

@@ -149,7 +149,7 @@ int swr_geometry(int in_rate, int out_rate, int *L, int *M) {
 // FFALIGN(filter_length, 8) floats.  An input above 192 kHz / 0.97 (352.8 / 384 / 705.6 /
 // 768 kHz) is DOWNsampled with the longer, narrower filter.  Equal rates: no resampler
 // (ffmpeg only converts the sample format), the 32-tap identity row.
-int swr_filter(int in_rate, int out_rate, int *taps, int *alloc, double *factor) {
+int swr_filter(int in_rate, int out_rate, int *taps, int *alloc, double *factor, int max_alloc) {
     if (in_rate <= 0 || out_rate <= 0) return -1;
     double f = out_rate * 0.97 / in_rate;
     if (f > 1.0 || in_rate == out_rate) f = 1.0;
@@ -157,7 +157,7 @@ int swr_filter(int in_rate, int out_rate, int *taps, int *alloc, double *factor)
     if (t < 1) t = 1;
     if (t > 1) t = (t + 1) & ~1;
     const int al = (t + 7) & ~7;
-    if (al > AMX_SWR_MAX_ALLOC) return -1;
+    if (al > max_alloc) return -1;
     if (taps) *taps = t;
     if (alloc) *alloc = al;
     if (factor) *factor = f;
@@ -167,9 +167,10 @@ int swr_filter(int in_rate, int out_rate, int *taps, int *alloc, double *factor)
 // resample_init: phase_count 1 << phase_shift (1024), replaced by the exact out / gcd
 // when that is <= 1024 (exact_rational).  The interpolating (1024-phase) form is restated
 // for the 32-tap filter only.
-int swr_phases(int in_rate, int out_rate) {
+int swr_phases(int in_rate, int out_rate, int max_alloc) {
     int L, M, t;
-    if (swr_geometry(in_rate, out_rate, &L, &M) || swr_filter(in_rate, out_rate, &t, nullptr, nullptr)) return -1;
+    if (swr_geometry(in_rate, out_rate, &L, &M) || swr_filter(in_rate, out_rate, &t, nullptr, nullptr, max_alloc))
+        return -1;
     if (L > 1024 && t != 32) return -1;
     return L <= 1024 ? L : 1024;
 }
@@ -209,11 +210,11 @@ static double swr_bessel(double x) {
 // build_filter (Kaiser beta 9, FLTP, scale 1): pc rows of filter_alloc floats (zeros past
 // filter_length); factor 1 forms sin(x) / x from an alternating sine table, factor < 1
 // from sin(x) itself
-int swr_bank(int in_rate, int out_rate, float *bank) {
-    const int pc = swr_phases(in_rate, out_rate);
+int swr_bank(int in_rate, int out_rate, float *bank, int max_alloc) {
+    const int pc = swr_phases(in_rate, out_rate, max_alloc);
     int taps = 0, alloc = 0;
     double factor = 1.0;
-    if (pc < 0 || swr_filter(in_rate, out_rate, &taps, &alloc, &factor)) return -1;
+    if (pc < 0 || swr_filter(in_rate, out_rate, &taps, &alloc, &factor, max_alloc)) return -1;
     const int center = (taps - 1) / 2;
     const int ph_nb = pc % 2 ? pc : pc / 2 + 1;
     std::vector<double> sin_lut(ph_nb), tab(taps);

@@ -12,12 +12,15 @@
 
 namespace amx {
 
-// libswresample's resampler geometry and filter bank for the 192 kHz measurement stream
+// libswresample's resampler geometry and filter bank for the 192 kHz measurement stream.
+// max_alloc: the widest row (filter_alloc) the caller takes; the measurement kernels hold
+// AMX_SWR_MAX_ALLOC, the output resampler (amx_resample.hip) AMX_RS_MAX_ALLOC
 int swr_geometry(int in_rate, int out_rate, int *L, int *M);
-int swr_filter(int in_rate, int out_rate, int *taps, int *alloc, double *factor);
-int swr_phases(int in_rate, int out_rate);
+int swr_filter(int in_rate, int out_rate, int *taps, int *alloc, double *factor,
+               int max_alloc = AMX_SWR_MAX_ALLOC);
+int swr_phases(int in_rate, int out_rate, int max_alloc = AMX_SWR_MAX_ALLOC);
 int swr_incr(int in_rate, int out_rate, int64_t *src_incr, int64_t *dst_incr);
-int swr_bank(int in_rate, int out_rate, float *bank);
+int swr_bank(int in_rate, int out_rate, float *bank, int max_alloc = AMX_SWR_MAX_ALLOC);
 
 using Mat = std::vector<double>;        // row-major D x D
 using MatL = std::vector<long double>;

@@ -17,6 +17,8 @@
 #define AMX_EQC 64        // compact EQ coefficient block (see ChainDev::eqc)
 #define AMX_MEAS_RATE 192000  // loudnorm pass 1 measures at 192 kHz (af_loudnorm dynamic mode)
 #define AMX_SWR_MAX_ALLOC 144   // the widest resampler row (filter_alloc) restated
+#define AMX_RS_MAX_ALLOC 256    // the output resampler's widest row (amx_resample.hip; factor >= 1 / 8)
+#define AMX_RS_TILE 256         // output frames per workgroup of k_resample
 // pass 1 for float32 stereo input with the analog stage: k_analog_h + k_gemv16 (the odd
 // tanh table's half in LDS; default), or k_front1s with the full table in global memory
 // (a table that is not odd; AMX_F1 = 2 forces it, for tests)

@@ -54,7 +54,9 @@ extern "C" {
  * of order 1..8 in the FLAC output); the two older entry points are the _ex forms with
  * lpc_order 0 and give the same sizes and bytes as before.
  * 6 (unchanged): amx_flac_scan and amx_flac_decode_device added (FLAC input decoded on the
- * device) with their two structures and AMX_EUNSUPPORTED; nothing that existed changed. */
+ * device) with their two structures and AMX_EUNSUPPORTED; nothing that existed changed.
+ * 6 (unchanged): amx_resample_size, amx_resampler_create / _run / _free added (the master
+ * at a chosen sample rate); nothing that existed changed. */
 #define AMX_ABI_VERSION 6
 
 #if defined(__GNUC__)
@@ -636,6 +638,36 @@ AMX_API int amx_mc_peak_pick(const int16_t *d_y, int64_t frames, int32_t channel
 AMX_API int amx_mc_limiter_out(const amx_plan *plan, const amx_final_desc *fd, const int16_t *d_y,
                                int32_t channels, const double *d_gains, const int32_t *d_ctl,
                                const double *d_att, int16_t *d_out, void *stream);
+
+/* ---------------------------------------------------------------------------------
+ * (ABI 6, added without a layout change) The finished master at another sample rate
+ * (DESIGN.md 3.12): libswresample's float (FLTP) resampler with its defaults (filter_size
+ * 32, cutoff 0.97, Kaiser beta 9, exact_rational) on int16 frames, then its f32 -> s16
+ * conversion -- `ffmpeg -i master.wav -af aresample=R:internal_sample_fmt=fltp`, as
+ * oracle/amx_oracle.c restates it (orc_upsample).  d_in int16 [frames][channels]
+ * interleaved -> d_out int16 [out_frames][channels], out_frames = ceil(frames L / M) with
+ * L / M = out_rate / in_rate reduced.  Replaces no reference line: the reference writes the
+ * master at the rate its last filter leaves (:223), 192 kHz after loudnorm's dynamic mode.
+ * Pairs: L <= 1024 (no output interpolates between phases) and a filter row of at most 256
+ * taps (out_rate >= in_rate / 7.76): every pair of 11.025, 22.05, 32, 44.1, 48, 88.2, 96,
+ * 176.4 and 192 kHz within that ratio.
+ * amx_resample_size (host only, no HIP call): the output frames of `frames` input frames,
+ * filter_length, filter_alloc and the phase count L; any output pointer may be NULL.
+ * AMX_EINVAL: a rate <= 0, equal rates, frames < 0; AMX_ERANGE: a pair outside the set.
+ * amx_resampler_create: builds and uploads the filter bank (allocates and copies
+ * synchronously: not inside a graph capture); the same errors, AMX_EINVAL for channels
+ * outside 1..8.  amx_resampler_run: one kernel on the stream, arguments validated before
+ * the launch, no allocation, no synchronisation; frames == 0 returns AMX_OK without a
+ * launch; AMX_EINVAL for a NULL handle or pointer, frames < 0 or out_capacity_frames below
+ * amx_resample_size's out_frames (nothing is written).  Exactly out_frames x channels
+ * samples are written.  amx_resampler_free accepts NULL. */
+typedef struct amx_resampler amx_resampler;
+AMX_API int amx_resample_size(int32_t in_rate, int32_t out_rate, int64_t frames, int64_t *out_frames,
+                              int32_t *taps, int32_t *alloc, int32_t *phases);
+AMX_API int amx_resampler_create(int32_t in_rate, int32_t out_rate, int32_t channels, amx_resampler **out);
+AMX_API int amx_resampler_run(const amx_resampler *h, const int16_t *d_in, int64_t frames, int16_t *d_out,
+                              int64_t out_capacity_frames, void *stream);
+AMX_API void amx_resampler_free(amx_resampler *h);
 
 #ifdef __cplusplus
 }
