@@ -460,7 +460,7 @@ __global__ void __launch_bounds__(1024) k_analog_h(const ChainDev *__restrict__ 
 // (chunk rows are 16-frame aligned); frames at or past a row's length load as 0.  The
 // accumulation order is k_front1s's, so e is the same to the bit.
 #define AMX_G16_PITCH (AMX_TF + 4)   // dwords per LDS row (16-B aligned rows)
-template <int D>
+template <int D, bool GS>
 __global__ void __launch_bounds__(AMX_BLOCK, 4) k_gemv16(const ChainDev *__restrict__ cdp,
                                                          const ChunkDev *__restrict__ chunks,
                                                          const SegDev *__restrict__ segs,
@@ -509,7 +509,7 @@ __global__ void __launch_bounds__(AMX_BLOCK, 4) k_gemv16(const ChainDev *__restr
 #pragma unroll
     for (int d = 0; d < H; d++) { a0[d] = 0.0; a1[d] = 0.0; }
     fetch(0);
-    const uint32_t *rp = s_in + row * AMX_G16_PITCH;
+    const int16_t *rp = reinterpret_cast<const int16_t *>(s_in + row * AMX_G16_PITCH);
     for (int k = 0; k < L; k += AMX_TF) {
 #pragma unroll
         for (int m = 0; m < 2; m++) {
@@ -521,14 +521,22 @@ __global__ void __launch_bounds__(AMX_BLOCK, 4) k_gemv16(const ChainDev *__restr
             v.w = n + 3 < ilen[m] ? v.w : 0u;
             *reinterpret_cast<uint4 *>(s_in + ((t >> 2) + 64 * m) * AMX_G16_PITCH + c4) = v;
         }
-        if (t < GQ) reinterpret_cast<uint4 *>(sG)[t] = RG;
+        if (t < GQ) {
+            // GS: the tile's rows as g 2^-15 (two multiplies per lane and tile; exact,
+            // the plan checked that no scaled entry is subnormal), so that the frame
+            // loop feeds (double)q -- fma(g 2^-15, q, acc) rounds the same real number
+            // as fma(g, q 2^-15, acc), and q 2^-15 == (double)((float)q / 32768.0f)
+            double2 gq = *reinterpret_cast<const double2 *>(&RG);
+            if constexpr (GS) { gq.x *= 0x1p-15; gq.y *= 0x1p-15; }
+            reinterpret_cast<double2 *>(sG)[t] = gq;
+        }
         __syncthreads();
         fetch(k + AMX_TF < L ? k + AMX_TF : k);
 #pragma unroll 1
         for (int f = 0; f < AMX_TF; f++) {
-            const uint32_t w = rp[f];
-            const double x0 = (double)((float)lo16(w) / 32768.0f);
-            const double x1 = (double)((float)hi16(w) / 32768.0f);
+            const int q0 = rp[2 * f], q1 = rp[2 * f + 1];   // sign-extending LDS reads
+            const double x0 = GS ? (double)q0 : (double)((float)q0 / 32768.0f);
+            const double x1 = GS ? (double)q1 : (double)((float)q1 / 32768.0f);
             const double *g = sG + f * D + half * H;
 #pragma unroll
             for (int d = 0; d < H; d++) {
@@ -549,9 +557,9 @@ __global__ void __launch_bounds__(AMX_BLOCK, 4) k_gemv16(const ChainDev *__restr
 // One thread per (segment, channel): lanes 2i / 2i+1 are the L / R channel of row
 // i.  The EQ runs stage-major over sub-tiles of AMX_EQ_F frames (eq_tile), so only
 // one stage's coefficients and a few frames are live: ~90 VGPRs, 5 waves/SIMD to
-// cover the fp64 recursion latency.  Width couples the channels: the pair
-// exchanges its float32 EQ output with one DPP swap per frame.  Tiles are fetched
-// one ahead (tile_fetch / tile_put).
+// cover the fp64 recursion latency.  Width couples the channels: each lane
+// adds the other's float32 EQ output, and its lane-signed copy, through DPP: two adds per
+// frame (amx_dev.hpp width_lane).  Tiles are fetched one ahead (tile_fetch / tile_put).
 // MB: also accumulate the crossover's zero-state end state (GEMV) for its scan.
 // KW (no multiband, K-filter segments == these segments): also the loudness pass-1
 // work on the output just produced -- the K filter's zero-state end state (GEMV
@@ -641,7 +649,8 @@ __device__ __forceinline__ VRows vt_rows(int32_t base, int len) {
 // SC: a stream chain (amx_chain_desc.stream_chain; no width): the input through slut
 // when given (as k_front1), and the EQ's float64 result clipped and scaled in float64
 // (:273-275 keep a 1-D stream's float64 result; float32 only when no stage ran)
-template <int MASK, bool MB, bool KW, bool SC = false>
+// GS (with MB): Gx holds the rows scaled by 2^-15 (amx_plan_build.cpp lti_models)
+template <int MASK, bool MB, bool KW, bool SC = false, bool GS = false>
 __global__ void __launch_bounds__(AMX_BLOCK, (MB || KW) ? 4 : 5) k_front2(const ChainDev *__restrict__ cdp,
                                                       const ChunkDev *__restrict__ chunks,
                                                       const SegDev *__restrict__ segs, int n_seg,
@@ -694,7 +703,7 @@ __global__ void __launch_bounds__(AMX_BLOCK, (MB || KW) ? 4 : 5) k_front2(const 
     const int klen = (j < n_seg) ? segs[j].len : 0;
     const int negm = (cd.st[0].neg ? 1 : 0) | (cd.st[3].neg ? 8 : 0);
     const float w = cd.width;
-    const int won = cd.width_on;
+    const bool won = !SC && cd.width_on;
     // tiles are wave-local: a wave stages, computes and stores only its own 32 rows
     // (the vector mover), so it never waits for the other waves of the workgroup
     const VRows vin = vt_rows(b_in, len);
@@ -706,7 +715,9 @@ __global__ void __launch_bounds__(AMX_BLOCK, (MB || KW) ? 4 : 5) k_front2(const 
         vt_put(s_in, R, vin, k);
         amx_wave_sync();
         vt_next(R, a16, vin, k, L);
-        const uint32_t *rp = s_in + row * AMX_VT_PITCH;
+        // the lane's channel of the row as int16 (sign-extending 16-bit LDS reads: no
+        // shift by the channel and no extension in the VALU)
+        const int16_t *rp = reinterpret_cast<const int16_t *>(s_in + row * AMX_VT_PITCH) + chn;
         uint32_t *op = s_out + row * AMX_VT_PITCH;
 #pragma unroll 1
         for (int f0 = 0; f0 < AMX_TF; f0 += AMX_EQ_F) {
@@ -714,33 +725,43 @@ __global__ void __launch_bounds__(AMX_BLOCK, (MB || KW) ? 4 : 5) k_front2(const 
             double x[AMX_EQ_F];
 #pragma unroll
             for (int f = 0; f < AMX_EQ_F; f++) {
-                const uint32_t p = rp[f0 + f];
-                const int16_t sv = chn ? hi16(p) : lo16(p);
-                if constexpr (SC) xf[f] = slut ? slut[(int)sv + 32768] : (float)sv / 32768.0f;
-                else xf[f] = (float)sv / 32768.0f;
-                x[f] = (double)xf[f];
+                const int sv = rp[2 * (f0 + f)];
+                if constexpr (SC) {
+                    xf[f] = slut ? slut[sv + 32768] : (float)sv / 32768.0f;
+                    x[f] = (double)xf[f];
+                } else {
+                    // (double)((float)sv / 32768.0f) == sv 2^-15 exactly (an int16 is a
+                    // float32, the division by 2^15 and the widening are exact), so the
+                    // float64 input is formed from the int; the float32 one is computed
+                    // only on the paths that read it (a negative first shelf, MASK 0)
+                    xf[f] = (float)sv / 32768.0f;
+                    x[f] = (double)sv * 0x1p-15;
+                }
             }
             // cd.pad0_ == 0: the offset makes the coefficient address depend on the
-            // loop, so the scalar loads stay per tile (no hoisting, no SGPR spill)
-            eq_tile<MASK, AMX_EQ_F>(negm, cd.eqc + (f0 & cd.pad0_), est, x, xf);
+            // loop, so the scalar loads stay per tile (no hoisting, no SGPR spill); the
+            // second peak stage's through an offset of its own, so that its loads are not
+            // merged with the first's (a load spanning both stages keeps both live)
+            eq_tile<MASK, AMX_EQ_F>(negm, cd.eqc + (f0 & cd.pad0_), cd.eqc + ((f0 + 1) & cd.pad0_), est, x, xf);
 #pragma unroll
             for (int f = 0; f < AMX_EQ_F; f++) {
-                int16_t qv;
+                int q;
                 if constexpr (SC) {
-                    qv = MASK ? f64_to_s16(x[f]) : f32_to_s16(xf[f]);
+                    q = MASK ? f64_to_q16(x[f]) : f32_to_q16(xf[f]);
                 } else {
                     float v = MASK ? (float)x[f] : xf[f];
-                    if (won) {
-                        const float o = pair_swap(v);
-                        v = width_one(w, chn ? o : v, chn ? v : o, chn);
-                    }
-                    qv = f32_to_s16(v);
+                    if (won) v = width_lane(w, chn, v);
+                    q = f32_to_q16(v);
                 }
-                const int other = __builtin_amdgcn_update_dpp(0, (int)qv, 0xB1, 0xF, 0xF, false);
-                if (chn == 0) op[f0 + f] = pack2(qv, (int16_t)other);
+                const int other = pair_other(q);
+                if (chn == 0) op[f0 + f] = pack2_lo(q, other);
                 if constexpr (MB) {
+                    // GS: the rows hold g 2^-15 (exact: the plan checked that none is
+                    // subnormal), and fma(g 2^-15, q, acc) rounds the same real number
+                    // as fma(g, q 2^-15, acc) -- the float32 detour of the input
+                    // ((double)((float)q / 32768.0f) == q 2^-15) is not needed
                     const double *g = Gx + (int64_t)(k + f0 + f) * AMX_XO_DIM;
-                    const double xd = (double)((float)qv / 32768.0f);
+                    const double xd = GS ? (double)q : (double)((float)q / 32768.0f);
 #pragma unroll
                     for (int d = 0; d < AMX_XO_DIM; d++) xv[d] = fma(g[d], xd, xv[d]);
                 }
@@ -750,8 +771,8 @@ __global__ void __launch_bounds__(AMX_BLOCK, (MB || KW) ? 4 : 5) k_front2(const 
                     // re-done right-aligned by k_peak_reduce (kw_fix)
                     const int n = k + f0 + f;
                     const bool act = n < klen;
-                    kmax = max(kmax, act ? abs((int)qv) : 0);
-                    const double xs = act ? (double)qv * (1.0 / 32768.0) : 0.0;
+                    kmax = max(kmax, act ? abs(q) : 0);
+                    const double xs = act ? (double)q * (1.0 / 32768.0) : 0.0;
                     const double *g = Gkw + (int64_t)n * AMX_KW_DIM;
 #pragma unroll
                     for (int d = 0; d < AMX_KW_DIM; d++) kv[d] = fma(g[d], xs, kv[d]);
@@ -842,32 +863,30 @@ __global__ void __launch_bounds__(AMX_BLOCK) k_xover2(const ChainDev *__restrict
         vt_put(si, R, vr, k);
         amx_wave_sync();
         vt_next(R, p16, vr, k, L);
-        uint32_t xin[AMX_TF];
+        // the lane's channel of the row as int16 (16-bit LDS reads: no shift by the channel)
+        int xin[AMX_TF];
 #pragma unroll
-        for (int q = 0; q < AMX_TF / 4; q++) {
-            const vt4 v = *reinterpret_cast<const vt4 *>(si + row * AMX_VT_PITCH + 4 * q);
-            xin[4 * q] = v.x; xin[4 * q + 1] = v.y; xin[4 * q + 2] = v.z; xin[4 * q + 3] = v.w;
-        }
+        for (int f = 0; f < AMX_TF; f++)
+            xin[f] = reinterpret_cast<const int16_t *>(si + row * AMX_VT_PITCH)[2 * f + chn];
         const int o = row * AMX_VT_PITCH;
 #pragma unroll 4
         for (int f = 0; f < AMX_TF; f++) {
-            const uint32_t p = xin[f];
-            const int16_t v = chn ? hi16(p) : lo16(p);
-            const double x = (double)((float)v / 32768.0f);   // :300 float32 then float64
+            // :300 float32 then float64: (double)((float)v / 32768.0f) == v 2^-15 exactly
+            // (an int16 is a float32; the division by 2^15 and the widening are exact)
+            const double x = (double)xin[f] * 0x1p-15;
             double l = bq_step(c, z[0], z[1], x);
             l = bq_step(c + 5, z[2], z[3], l);
             double h = bq_step(c + 10, z[4], z[5], x);
             h = bq_step(c + 15, z[6], z[7], h);
             const double m = (x - l) - h;                      // :304
-            const int ql = f64_to_s16(l), qm = f64_to_s16(m), qh = f64_to_s16(h);
-            const int ol = __builtin_amdgcn_update_dpp(0, ql, 0xB1, 0xF, 0xF, false);
-            const int om = __builtin_amdgcn_update_dpp(0, qm, 0xB1, 0xF, 0xF, false);
-            const int oh = __builtin_amdgcn_update_dpp(0, qh, 0xB1, 0xF, 0xF, false);
+            // (ints in [-32767, 32767]: no narrowing; every lane is active: pair_other)
+            const int ql = f64_to_q16(l), qm = f64_to_q16(m), qh = f64_to_q16(h);
+            const int ol = pair_other(ql), om = pair_other(qm), oh = pair_other(qh);
             if (chn == 0) {
-                slo[o + f] = pack2((int16_t)ql, (int16_t)ol);
-                smi[o + f] = pack2((int16_t)qm, (int16_t)om);
+                slo[o + f] = pack2_lo(ql, ol);
+                smi[o + f] = pack2_lo(qm, om);
             } else {
-                shi[o + f] = pack2((int16_t)oh, (int16_t)qh);
+                shi[o + f] = pack2_lo(oh, qh);
             }
         }
         amx_wave_sync();
@@ -916,8 +935,13 @@ static hipError_t front1s_t(const Launch &l, const uint32_t *in, const float *lu
                 hipLaunchKernelGGL(k_analog_h<false>, gh, dim3(1024), 0, l.stream, l.cd, l.chunks, l.n_chunks,
                                    reinterpret_cast<const float *>(in), l.lut_half, a16, l.an_blocks);
             if constexpr (D > 0) {
-                hipLaunchKernelGGL((k_gemv16<D>), dim3((unsigned)((l.n_seg + rows - 1) / rows)), dim3(AMX_BLOCK), 0,
-                                   l.stream, l.cd, l.chunks, l.segs, l.n_seg, l.L, a16, G, e);
+                const dim3 gg((unsigned)((l.n_seg + rows - 1) / rows));
+                if (l.gin_scaled)
+                    hipLaunchKernelGGL((k_gemv16<D, true>), gg, dim3(AMX_BLOCK), 0, l.stream, l.cd, l.chunks,
+                                       l.segs, l.n_seg, l.L, a16, G, e);
+                else
+                    hipLaunchKernelGGL((k_gemv16<D, false>), gg, dim3(AMX_BLOCK), 0, l.stream, l.cd, l.chunks,
+                                       l.segs, l.n_seg, l.L, a16, G, e);
             }
             return hipGetLastError();
         }
@@ -957,13 +981,13 @@ hipError_t launch_front1(const Launch &l, int D, int win, bool analog, const flo
     return hipErrorInvalidValue;
 }
 
-template <int MASK, bool MB, bool KW, bool SC = false>
+template <int MASK, bool MB, bool KW, bool SC = false, bool GS = false>
 static hipError_t front2_t(const Launch &l, const uint32_t *a16, const double *s_eq,
                            uint32_t *dst, int to_out, const double *Gx, double *e_x,
                            const double *Gkw, double *e_kw, uint32_t *pk, const float *slut = nullptr) {
     const int rows = AMX_BLOCK / 2;
     dim3 grid((unsigned)((l.n_seg + rows - 1) / rows));
-    hipLaunchKernelGGL((k_front2<MASK, MB, KW, SC>), grid, dim3(AMX_BLOCK), 0, l.stream, l.cd,
+    hipLaunchKernelGGL((k_front2<MASK, MB, KW, SC, GS>), grid, dim3(AMX_BLOCK), 0, l.stream, l.cd,
                        l.chunks, l.segs, l.n_seg, l.L, a16, s_eq, dst, to_out, Gx, e_x, Gkw, e_kw,
                        pk, slut);
     return hipGetLastError();
@@ -977,15 +1001,17 @@ hipError_t launch_front2(const Launch &l, int mask, const int16_t *a16, const do
     if (l.n_seg <= 0) return hipSuccess;
     const uint32_t *a = reinterpret_cast<const uint32_t *>(a16);
     uint32_t *d = reinterpret_cast<uint32_t *>(dst);
-    const bool mb = Gx != nullptr, kw = Gkw != nullptr;
+    const bool mb = Gx != nullptr, kw = Gkw != nullptr, gs = l.gin_scaled != 0;
     if (mb && kw) return hipErrorInvalidValue;
     if (sc && kw) return hipErrorInvalidValue;          // a stream chain measures elsewhere
     switch (mask) {
 #define C2(M)                                                                           \
     case M:                                                                             \
-        if (sc) return mb ? front2_t<M, true, false, true>(l, a, s_eq, d, to_out, Gx, e_x, Gkw, e_kw, pk, slut) \
+        if (sc) return mb && gs ? front2_t<M, true, false, true, true>(l, a, s_eq, d, to_out, Gx, e_x, Gkw, e_kw, pk, slut) \
+                     : mb ? front2_t<M, true, false, true>(l, a, s_eq, d, to_out, Gx, e_x, Gkw, e_kw, pk, slut) \
                           : front2_t<M, false, false, true>(l, a, s_eq, d, to_out, Gx, e_x, Gkw, e_kw, pk, slut); \
-        return mb ? front2_t<M, true, false>(l, a, s_eq, d, to_out, Gx, e_x, Gkw, e_kw, pk) \
+        return mb && gs ? front2_t<M, true, false, false, true>(l, a, s_eq, d, to_out, Gx, e_x, Gkw, e_kw, pk) \
+             : mb ? front2_t<M, true, false>(l, a, s_eq, d, to_out, Gx, e_x, Gkw, e_kw, pk) \
              : kw ? front2_t<M, false, true>(l, a, s_eq, d, to_out, Gx, e_x, Gkw, e_kw, pk) \
                   : front2_t<M, false, false>(l, a, s_eq, d, to_out, Gx, e_x, Gkw, e_kw, pk);
         AMX_MASK_CASES(C2)

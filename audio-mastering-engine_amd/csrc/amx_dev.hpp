@@ -25,6 +25,19 @@ __device__ __forceinline__ double f64_clip1_raw(double x);
 __device__ __forceinline__ int16_t f64_to_s16(double x) {
     return (int16_t)(int)(f64_clip1_raw(x) * 32767.0);
 }
+// f32_to_s16 / f64_to_s16 as an int, for the segment kernels: the clipped value times
+// 32767 lies in [-32767, 32767], so the narrowing to int16 changes nothing and its
+// sign extension (a v_bfe_i32 per sample) is left out
+__device__ __forceinline__ int f32_to_q16(float x) {
+    return (int)(__builtin_amdgcn_fmed3f(x, -1.0f, 1.0f) * 32767.0f);
+}
+__device__ __forceinline__ int f64_to_q16(double x) {
+    return (int)(f64_clip1_raw(x) * 32767.0);
+}
+// the low halves of two words as one (pack2 of two int16 held in ints): one v_perm_b32
+__device__ __forceinline__ uint32_t pack2_lo(int a, int b) {
+    return __builtin_amdgcn_perm((uint32_t)b, (uint32_t)a, 0x05040100u);
+}
 // "%.2f" then float(): the exact decimal rounding (half-even on exact ties) of v (the
 // loudnorm statistics strings the reference parses, :237-241)
 __device__ __forceinline__ double round2(double v) {
@@ -193,10 +206,14 @@ __device__ __forceinline__ float eq_chain(int negm, const double *q, double *z, 
 
 // Stage-major form of eq_chain over F frames of one channel (amx_chain.hip k_front2):
 // each stage runs over all F frames before the next, so only that stage's
-// coefficients are live, as SGPR operands of the FMAs.  The two peak stages share
-// one loop body (`#pragma unroll 1`) over a per-iteration coefficient address, with
-// their 8-double states swapped between iterations; otherwise the compiler hoists
-// and merges every stage's scalar loads (~54 doubles > the SGPR file) and spills.
+// coefficients are live, as SGPR operands of the FMAs.  The two peak stages are two
+// copies of one body (eq_peak), each on its own 8-double state (pa, pb): as one
+// `#pragma unroll 1` loop they swapped the states between iterations, 16 v_mov_b64 per
+// iteration.  A scheduling barrier between the copies keeps the second stage's scalar
+// loads behind the first stage's arithmetic (the caller's loop-dependent coefficient
+// address keeps them in the loop); without it the compiler merges every stage's loads
+// (~54 doubles > the SGPR file) and spills.  The arithmetic and its order are those of
+// the loop form: the same bits.
 // Inside a stage the unrolled section x frame grid is one basic block, so section
 // k+1 of frame f overlaps section k of frame f+1.
 struct EqState {
@@ -223,9 +240,33 @@ __device__ __forceinline__ void eq_state_load(EqState &st, const double *z) {
     if constexpr ((MASK & 8) != 0) { st.s3[0] = z[o]; st.s3[1] = z[o + 1]; }
 }
 
+template <int F>
+__device__ __forceinline__ void eq_peak(const double *__restrict__ q, double *pz, double *x) {
+    double b[F];
+#pragma unroll
+    for (int f = 0; f < F; f++) b[f] = x[f];
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+#pragma unroll
+        for (int f = 0; f < F; f++)
+            b[f] = bq_step(q + 5 * k, pz[2 * k], pz[2 * k + 1], b[f]);
+    const double gm1 = q[20];
+#pragma unroll
+    for (int f = 0; f < F; f++) x[f] = x[f] + b[f] * gm1;
+    // the stage's end state is formed here: left to the compiler, the last frame's state
+    // updates sink to the end of the caller's sub-tile (their results are not read before
+    // the next one) and keep this stage's coefficients live in SGPRs across the stages
+    // after it, which spills
+#pragma unroll
+    for (int i = 0; i < 8; i++) asm volatile("" : "+v"(pz[i]));
+}
+
+// xf: the float32 input, read only where a negative-gain shelf is the first active stage;
+// sq2 == sq through another address computation: the second peak stage's coefficients
 template <int MASK, int F>
-__device__ __forceinline__ void eq_tile(int negm, const double *__restrict__ sq, EqState &st,
-                                        double *x, const float *xf) {
+__device__ __forceinline__ void eq_tile(int negm, const double *__restrict__ sq,
+                                        const double *__restrict__ sq2, EqState &st, double *x,
+                                        const float *xf) {
     constexpr int NP = ((MASK >> 1) & 1) + ((MASK >> 2) & 1);
     int c = 0;
     if constexpr ((MASK & 1) != 0) {
@@ -251,24 +292,14 @@ __device__ __forceinline__ void eq_tile(int negm, const double *__restrict__ sq,
         c = 6;
     }
     if constexpr (NP > 0) {
-#pragma unroll 1
-        for (int sidx = 0; sidx < NP; sidx++) {
-            const double *q = sq + c + 21 * sidx;
-            double b[F];
-#pragma unroll
-            for (int f = 0; f < F; f++) b[f] = x[f];
-#pragma unroll
-            for (int k = 0; k < 4; k++)
-#pragma unroll
-                for (int f = 0; f < F; f++)
-                    b[f] = bq_step(q + 5 * k, st.pa[2 * k], st.pa[2 * k + 1], b[f]);
-            const double gm1 = q[20];
-#pragma unroll
-            for (int f = 0; f < F; f++) x[f] = x[f] + b[f] * gm1;
-            if constexpr (NP == 2) {
-#pragma unroll
-                for (int i = 0; i < 8; i++) { const double tmp = st.pa[i]; st.pa[i] = st.pb[i]; st.pb[i] = tmp; }
-            }
+        // (barriers where the loop form had its boundaries: each stage's loads and
+        // arithmetic stay a scheduling region of their own)
+        __builtin_amdgcn_sched_barrier(0);
+        eq_peak<F>(sq + c, st.pa, x);
+        __builtin_amdgcn_sched_barrier(0);
+        if constexpr (NP == 2) {
+            eq_peak<F>(sq2 + c + 21, st.pb, x);
+            __builtin_amdgcn_sched_barrier(0);
         }
         c += 21 * NP;
     }
@@ -306,10 +337,45 @@ __device__ __forceinline__ void width_frame(float w, float &l, float &r) {
     l = __builtin_amdgcn_fmed3f(nl, -1.0f, 1.0f);
     r = __builtin_amdgcn_fmed3f(nr, -1.0f, 1.0f);
 }
-// the one channel a lane keeps (chn 0: left = clip(mid + side), 1: right = clip(mid - side))
-__device__ __forceinline__ float width_one(float w, float l, float r, int chn) {
-    const float mid = (l + r) / 2.0f, side = ((l - r) / 2.0f) * w;
-    return __builtin_amdgcn_fmed3f(chn ? mid - side : mid + side, -1.0f, 1.0f);
+// The one channel a lane keeps, before the clip (the int16 conversion that follows clips:
+// f32_to_q16).  Both lanes run the same instructions on lane-signed values -- two selects
+// of a sign, where choosing l and r by the channel took three selects and kept the
+// exchange out of the sums.  e = width_sign(v, chn) is the lane's sample with the right
+// one negated; a, b = the lane's own sample and the pair's other one, ea, eb = their e.
+//   left  (a = l, b = r, ea = l, eb = -r):  mid = (l + r) / 2; ea + eb = l + (-r) == l - r
+//     (IEEE subtraction is addition of the negation); side and mid + side are
+//     width_frame's, its nl.
+//   right (a = r, b = l, ea = -r, eb = l): r + l == l + r and (-r) + l == l - r (addition
+//     commutes), so mid and side are the left lane's floats, signed zeros included
+//     (l == r gives +0 in both); mid + (-side) == mid - side is width_frame's nr.
+// (Forming the difference as own - other in both lanes is an instruction less and is NOT
+// the same: for l == r both lanes get +0 where the right lane needs -(+0), and l = r = -0
+// then gives +0 for width_frame's -0.)  tests/test_chain_identities.py checks the pair
+// against width_frame bit for bit.
+__device__ __forceinline__ float width_sign(float v, int chn) {
+    return chn ? -v : v;
+}
+__device__ __forceinline__ float width_mix(float w, int chn, float sum, float dif) {
+    const float mid = sum / 2.0f, side = (dif / 2.0f) * w;
+    return mid + width_sign(side, chn);
+}
+__device__ __forceinline__ float width_self(float w, int chn, float a, float b, float ea, float eb) {
+    return width_mix(w, chn, a + b, ea + eb);
+}
+// a + (the pair's other lane's x) as one v_add_f32_dpp (every lane active).  Written out:
+// the compiler packs the two sums of width_self into a v_pk_add_f32 fed by two DPP moves,
+// an instruction more.  The s_nop covers the VALU-write -> DPP-read hazard, which the
+// compiler does not track into an asm.
+__device__ __forceinline__ float pair_add(float a, float x) {
+    float r;
+    asm("s_nop 1\n\tv_add_f32_dpp %0, %1, %2 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf bound_ctrl:1"
+        : "=v"(r) : "v"(x), "v"(a));
+    return r;
+}
+// width_self with the other lane's operands fetched inside the sums
+__device__ __forceinline__ float width_lane(float w, int chn, float a) {
+    const float e = width_sign(a, chn);
+    return width_mix(w, chn, pair_add(a, a), pair_add(e, e));
 }
 
 // ------------------------------------------------------- LDS tile stager
@@ -439,6 +505,15 @@ __device__ __forceinline__ void tile_store(const uint32_t *lds, uint32_t *__rest
 // the other lane of an even/odd lane pair (channel pairs, DPP quad_perm [1,0,3,2])
 __device__ __forceinline__ float pair_swap(float v) {
     return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, false));
+}
+// the same exchange for the segment kernels, which run it with every lane active: the
+// lanes a quad_perm reads are then always valid, so the move needs no old value (the
+// form above first writes its 0: a v_mov_b32 per exchange)
+__device__ __forceinline__ int pair_other(int v) {
+    return __builtin_amdgcn_mov_dpp(v, 0xB1, 0xF, 0xF, true);
+}
+__device__ __forceinline__ float pair_other(float v) {
+    return __int_as_float(pair_other(__float_as_int(v)));
 }
 __device__ __forceinline__ double pair_swap(double v) {
     const int64_t b = __double_as_longlong(v);

@@ -568,7 +568,7 @@ __global__ void __launch_bounds__(64 * AMX_ENV_WG) k_env0(const ChainDev *__rest
     // inside a compressed stretch the state sits at or near m, and trajectories meet
     // sooner from there than from 0 (scripts/env_warm_sim.py)
     double att = 0.0, s_spec = 0.0;
-    if (cd.env_guess && start >= 0) att = mt[mi[rowoff + start]];
+    if (start >= 0) att = mt[mi[rowoff + start]];
     bool any = false;
     for (int q0 = 0; q0 < ntile; q0 += AMX_ENV_PF) {
 #pragma unroll

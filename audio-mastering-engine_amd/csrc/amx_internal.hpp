@@ -42,6 +42,7 @@ struct Launch {
     int64_t max_chunk_n = 0;           // frames of the longest chunk (elementwise grids)
     int64_t an_blocks = 0;             // k_analog_h's 4096-frame blocks over all chunks
     int an_vec = 0;                    // every chunk: even in_off and >= 4 frames (k_analog_h<true>)
+    int gin_scaled = 0;                // GEMV rows over int16 input scaled by 2^-15 (amx_plan_build.cpp)
 };
 struct ScanPlan {
     int D, n_blk, K;

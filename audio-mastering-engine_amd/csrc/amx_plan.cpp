@@ -246,7 +246,7 @@ int amx_run_stage(amx_plan *p, int32_t stage, const float *d_in, int16_t *d_out,
     if (p->n_seg == 0) return AMX_OK;
     hipStream_t st = (hipStream_t)stream;
     amx::Launch l{p->d_cd, p->d_chunks, p->d_segs, p->n_chunks, p->n_seg, p->L, st, p->d_lut_half,
-                  p->f1_mode, p->max_chunk_n, p->an_blocks, p->an_vec};
+                  p->f1_mode, p->max_chunk_n, p->an_blocks, p->an_vec, p->gin_scaled};
     int16_t *a16 = wsp<int16_t>(d_ws, p->o_a16);
     double *e = wsp<double>(d_ws, p->o_e), *s = wsp<double>(d_ws, p->o_s);
     int16_t *p16 = p->mb ? wsp<int16_t>(d_ws, p->o_p16) : nullptr;

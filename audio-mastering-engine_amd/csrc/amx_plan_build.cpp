@@ -98,6 +98,16 @@ int64_t overlay_len(int64_t n, int fs) {
 
 }  // namespace
 
+// scales Gx by 2^-15 in place and returns true when every entry of G and Gx times 2^-15
+// is exact (zero, or still normal); else leaves both as they are (lti_models)
+bool scale_gemv_rows(const std::vector<double> &G, std::vector<double> &Gx) {
+    for (const std::vector<double> *t : {&G, static_cast<const std::vector<double> *>(&Gx)})
+        for (double g : *t)
+            if (!(g == 0.0 || std::fabs(g) >= 0x1p-1007)) return false;
+    for (double &g : Gx) g *= 0x1p-15;
+    return true;
+}
+
 Mat Lti::pow(int64_t p) const { return to_double(matpow(A, p, D)); }
 std::vector<double> Lti::gemv_table(int L) const {
     std::vector<double> G((size_t)L * D);
@@ -544,7 +554,6 @@ int Builder::compressor_tables() {
     cd.env_R = R;
     cd.env_rA = 1.0 / A;
     cd.env_rR = 1.0 / R;
-    cd.env_guess = 1;                                   // k_env0 still reads it
     cd.env_rcp = 1;
     for (size_t i = 0; i < (size_t)3 * 3 * 32769 && cd.env_rcp; i += 1) {
         if (i % (3 * 32769) >= 32769) continue;
@@ -873,6 +882,14 @@ int Builder::lti_models() {
         p->lev_x = xo.window_powers((int64_t)p->L * AMX_SCAN_S, tol, 16, p->Mpx);
         if (p->lev_x < 0) return fail(AMX_ERANGE, "crossover decays too slowly for %d-frame segments", p->L);
     }
+    // The int16 sample enters the GEMVs as q 2^-15.  With the rows scaled by 2^-15 the
+    // kernels feed (double)q: fma(g 2^-15, q, acc) and fma(g, q 2^-15, acc) round the
+    // same real number, as long as g 2^-15 is g's exact multiple -- it is unless it
+    // falls below the normal range.  k_front2 reads Gx scaled here; k_gemv16 scales the
+    // EQ rows (G, which the float32 front kernels read unscaled) as it stages them, so
+    // both tables are checked, and one entry that would be subnormal keeps the
+    // unscaled rows and the q / 32768 input for both (gin_scaled = 0).
+    p->gin_scaled = scale_gemv_rows(p->G, p->Gx) ? 1 : 0;
     Lti &kw = p->kw_model;
     kw.derive(AMX_KW_DIM, [&](LD *z, LD x) {
         LD y = sos_step_h(cd.kw1, z, x);

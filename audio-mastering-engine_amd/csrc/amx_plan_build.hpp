@@ -55,6 +55,10 @@ struct Lti {
     int window_powers(int64_t LS, double tol, int max_k, std::vector<double> &out) const;
 };
 
+// the GEMV rows over int16 input: Gx scaled by 2^-15 in place, true, when no scaled entry
+// of G or Gx would be subnormal; else both untouched, false (amx_plan_build.cpp)
+bool scale_gemv_rows(const std::vector<double> &G, std::vector<double> &Gx);
+
 // The two environment switches of plan construction, both for tests, with their
 // defaults.  from_env() is the only reader of the variables.
 struct PlanKnobs {
@@ -99,6 +103,10 @@ struct PlanHost {
     int64_t max_nkseg = 0;
     int64_t nloc = 0, out_frames = 0, max_chunk_out = 0, max_span = 0, max_chunk_n = 0;
     int64_t an_blocks = 0;      // k_analog_h's 4096-frame blocks over all chunks
+    // 1: the crossover GEMV rows (Gx) hold g 2^-15 and k_gemv16 scales its G tiles the
+    // same way, so both feed the int16 sample as (double)q (lti_models checks that no
+    // scaled entry is subnormal; 0 keeps q / 32768 as the input)
+    int gin_scaled = 0;
     int an_vec = 1;             // k_analog_h<true>: every chunk at an even input frame, >= 4 frames
     int64_t in_frames = 0;  // input frames the chunks read (max in_offset + frames)
     int64_t max_hops = 1;   // 100 ms hops of the longest track's measurement stream

@@ -64,9 +64,7 @@ struct ChainDev {
     // equal the IEEE quotient for every table value m (amx_dyn.hip env_div)
     double env_A, env_R, env_rA, env_rR;
     int32_t env_rcp;
-    // k_env0's warm-up start guess: 1 = m of the warm-up's first frame, 0 = att = 0
-    // 
-    int32_t env_guess;
+    int32_t pad1_;         // (the struct's size is recorded: tests/golden/plan_build.txt)
     // envelope segment tables by active-band count (amx_dyn.hip): table t (1..3) cuts
     // the chunks into segments of Le frames so that t bands' segments fill the CUs as
     // one resident wave set; k_rms flags the bands with a frame over the threshold and
