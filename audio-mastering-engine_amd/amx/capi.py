@@ -124,6 +124,7 @@ EXPORTS = ("amx_abi_version", "amx_last_error", "amx_build_id", "amx_plan_create
            "amx_plan_set_limiter_channels",
            "amx_mc_plan_create", "amx_mc_plan_free", "amx_mc_plan_get_info", "amx_mc_run_chunks",
            "amx_mc_split_pairs", "amx_mc_loudness_combine", "amx_mc_peak_pick", "amx_mc_limiter_out",
+           "amx_mc_loudnorm_192k_size", "amx_mc_loudnorm_192k",
            "amx_flac_encode_size", "amx_flac_encode", "amx_flac_encode_size_ex", "amx_flac_encode_ex",
            "amx_flac_scan", "amx_flac_decode_device",
            "amx_resample_size", "amx_resampler_create", "amx_resampler_run", "amx_resampler_free")
@@ -172,6 +173,10 @@ def load(path=None):
     L.amx_mc_loudness_combine.argtypes = [vp, ctypes.c_int64, vp, ctypes.c_int32, vp, vp, vp]
     L.amx_mc_peak_pick.argtypes = [vp, ctypes.c_int64, ctypes.c_int32, vp, vp, vp]
     L.amx_mc_limiter_out.argtypes = [vp, ctypes.POINTER(FinalDesc), vp, ctypes.c_int32, vp, vp, vp, vp, vp]
+    L.amx_mc_loudnorm_192k_size.argtypes = [vp, ctypes.c_int32, ctypes.POINTER(ctypes.c_int64),
+                                            ctypes.POINTER(ctypes.c_int64)]
+    L.amx_mc_loudnorm_192k.argtypes = [vp, ctypes.c_int32, ctypes.POINTER(LoudnormDesc), vp, vp, ctypes.c_int64,
+                                       vp, vp, vp, vp, vp]
     L.amx_kw_propagate.argtypes = [vp, ctypes.c_int64, c_double_p, c_double_p]
     L.amx_loudness_pass2.argtypes = [vp, vp, vp, vp, vp, ctypes.c_int64, vp, vp]
     L.amx_loudness_histograms.argtypes = [vp, vp, ctypes.c_int64, vp, vp, vp, vp]

@@ -22,7 +22,7 @@ import torch
 
 from . import capi, design, loudness
 from .chunking import plan_tracks, packet_frames
-from .settings import ALIMITER, LOUDNORM_LRA, LOUDNORM_TP, output_rate
+from .settings import ALIMITER, LOUDNORM_LRA, LOUDNORM_TP, multichannel_dynamic, output_rate
 
 
 class DynamicModeUnsupported(NotImplementedError):
@@ -468,9 +468,20 @@ class MasteringJob:
             self.run(d_in)
         torch.cuda.current_stream().wait_stream(s)
         g = torch.cuda.CUDAGraph()
-        # thread_local: other threads (a process group's watchdog) may query events meanwhile
-        with torch.cuda.graph(g, capture_error_mode="thread_local"):
-            self.run(d_in, dyn=not dyn)
+        # A plan the garbage collector frees on this thread while the stream captures (a
+        # dropped job in a reference cycle: amx_plan_free's hipFree) invalidates the capture:
+        # collect such jobs now and keep the collector off until the capture has ended.
+        import gc
+        gc.collect()
+        gc_was_on = gc.isenabled()
+        gc.disable()
+        try:
+            # thread_local: other threads (a process group's watchdog) may query events meanwhile
+            with torch.cuda.graph(g, capture_error_mode="thread_local"):
+                self.run(d_in, dyn=not dyn)
+        finally:
+            if gc_was_on:
+                gc.enable()
         self._graph = g
         self._dyn_eager = dyn
         if dyn and dyn_graph:
@@ -597,8 +608,12 @@ class MultiChannelJob:
                                 its peaks; histograms and the decision on a one-track plan;
       amx_mc_peak_pick + amx_finalize (att trace) + amx_mc_limiter_out -- the alimiter:
                                 its state depends only on each frame's largest |sample|.
-    Loudnorm's dynamic mode (:240 when the linear conditions fail) is not run for C > 2:
-    finish() raises DynamicModeUnsupported.  Parity: the chain is pinned bit-exact to the
+    Loudnorm's dynamic mode (:240 when the linear conditions fail): fetch_report() raises
+    DynamicModeUnsupported by default; dynamic(stats) runs it -- af_loudnorm's 192 kHz state
+    machine on the C channels, frame by frame on one workgroup (amx_mc_loudnorm_192k), the
+    192 kHz measurement and the C-channel alimiter at 192 kHz -- and master_array /
+    master_audio call it when the settings key multichannel_dynamic is True.
+    Parity: the chain is pinned bit-exact to the
     reference's own chunk body (tests/golden/mc*.npz); the measurement's channel weights
     and the C-channel alimiter are parity unpinned (ffmpeg is absent), checked against
     the oracle's restatement (oracle/amx_oracle.c)."""
@@ -614,6 +629,7 @@ class MultiChannelJob:
         self.fs, self.C = int(sample_rate), C
         self.settings = dict(settings)
         self.input_s16 = bool(input_s16)
+        self.limiter = limiter
         self.desc, self._keep = design.chain_desc(self.fs, C, self.settings)
         self.desc.input_s16 = 1 if input_s16 else 0
         if quantum is None:
@@ -707,11 +723,137 @@ class MultiChannelJob:
         self.measure(stream)
         return self.finalize(stream)
 
+    # --------------------------------------------- loudnorm dynamic mode (192 kHz)
+    def _side192(self):
+        """The 192 kHz side of the track, made once per job (creating a plan synchronises
+        the device): amx_mc_loudnorm_192k's scratch and output, a P-track and a one-track
+        measure plan at 192 kHz (the filter output's loudness gives pass 1's
+        target_offset) and the C-channel alimiter on the one-track plan (att trace,
+        amx_plan_set_limiter_channels), as __init__ sets them up at the input rate."""
+        side = getattr(self, "_s192", None)
+        if side is not None:
+            return side
+        import ctypes
+        from types import SimpleNamespace
+        L = capi.load()
+        C, dev = self.C, self.device
+        n192, wsb = ctypes.c_int64(), ctypes.c_int64()
+        capi.check(L.amx_mc_loudnorm_192k_size(self.meas.plan.h, C, ctypes.byref(n192), ctypes.byref(wsb)),
+                   "amx_mc_loudnorm_192k_size")
+        n = max(1, n192.value)
+        P = (C + 1) // 2
+        lufs = self.settings.get("lufs")
+        s = SimpleNamespace(n192=n192.value)
+        s.meas = MasteringJob(192000, 2, {"lufs": lufs}, [n] * P, input_s16=True,
+                              chunks=[(p, p * n, n) for p in range(P)], device=dev, measure_only=True,
+                              seg_frames=1024)              # the K scan's window at 192 kHz
+        s.one = MasteringJob(192000, 2, {"lufs": lufs}, [n], input_s16=True, chunks=[(0, 0, n)], device=dev,
+                             measure_only=True, seg_frames=1024, limiter=self.limiter)
+        s.att = torch.ones(n, dtype=torch.float64, device=dev)
+        capi.check(L.amx_plan_set_limiter_trace(s.one.plan.h, capi.ptr(s.att)), "amx_plan_set_limiter_trace")
+        capi.check(L.amx_plan_set_limiter_channels(s.one.plan.h, C), "amx_plan_set_limiter_channels")
+        s.ws = torch.empty(max(1, wsb.value), dtype=torch.uint8, device=dev)
+        s.y192 = torch.empty((n, C), dtype=torch.int16, device=dev)     # the filter's output
+        s.out = torch.empty_like(s.y192)                                  # the alimiter's
+        s.summ = torch.zeros(16, dtype=torch.float64, device=dev)
+        self._s192 = s
+        return s
+
+    def dyn_filter(self, desc, stream=None):
+        """amx_mc_loudnorm_192k on the measured track (measure() with lufs on has filled the
+        pairs, the combined hop energies and peaks) -> the side's y192"""
+        import ctypes
+        s = self._side192()
+        capi.check(capi.load().amx_mc_loudnorm_192k(
+            self.meas.plan.h, self.C, ctypes.byref(desc), capi.ptr(self.meas.out), capi.ptr(self.one.hops),
+            int(self.one.max_hops), capi.ptr(self.one.peak), capi.ptr(s.y192), capi.ptr(s.summ), capi.ptr(s.ws),
+            self._s(stream)), "amx_mc_loudnorm_192k")
+
+    def dyn_measure(self, stream=None, lufs_on=True):
+        """the 192 kHz measurement of the filter's output over the C channels (split pairs,
+        the P-track plan's passes, combine, histograms, decision); lufs off: the peaks only"""
+        L = capi.load()
+        s = self._side192()
+        st = self._s(stream)
+        capi.check(L.amx_mc_split_pairs(capi.ptr(s.y192), s.n192, self.C, capi.ptr(s.meas.out), st),
+                   "amx_mc_split_pairs")
+        s.meas.loudness_pass1(stream, tail=False)
+        if lufs_on:
+            s.meas.loudness_pass2(stream, carry=False)
+        capi.check(L.amx_mc_loudness_combine(capi.ptr(s.meas.hops), int(s.meas.max_hops), capi.ptr(s.meas.peak),
+                                             self.C, capi.ptr(s.one.hops), capi.ptr(s.one.peak), st),
+                   "amx_mc_loudness_combine")
+        if lufs_on:
+            s.one.histograms(stream)
+        s.one.dd.lufs_on = 1 if lufs_on else 0
+        s.one.decide(stream)
+
+    def dyn_limit(self, stream=None):
+        """:223 on the 192 kHz file: the C-channel alimiter over y192 -> the side's out.  Its
+        input bound is af_loudnorm's ceiling (ln_output_bound); a track under 3 s (the
+        unclamped linear fallback) measures it."""
+        L = capi.load()
+        s = self._side192()
+        st = self._s(stream)
+        bound = ln_output_bound(s.n192)
+        if bound is not None:
+            with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+                s.one.peak.fill_(bound)
+            s.one.dd.lufs_on = 0
+            s.one.decide(stream)
+        else:
+            self.dyn_measure(stream, lufs_on=False)
+        one = s.one
+        capi.check(L.amx_mc_peak_pick(capi.ptr(s.y192), s.n192, self.C, capi.ptr(one.gains), capi.ptr(one.out), st),
+                   "amx_mc_peak_pick")
+        one.finalize(None, stream)
+        capi.check(L.amx_mc_limiter_out(one.plan.h, one.fd, capi.ptr(s.y192), self.C, capi.ptr(one.gains),
+                                        capi.ptr(one.ctl), capi.ptr(s.att), capi.ptr(s.out), st),
+                   "amx_mc_limiter_out")
+
+    def dynamic(self, stats, stream=None):
+        """loudnorm's dynamic mode for the track (:240 when the linear conditions fail), the
+        twin of MasteringJob.dynamic_track for C channels: pass 1's filter with the
+        measured_* defaults; the 192 kHz measurement of its output, whose integrated
+        loudness gives target_offset ("%.2f"); pass 2's filter with the track's pass-1
+        strings `stats` (fetch_report's) and that offset, on pass 1's 192 kHz stream; the
+        C-channel alimiter at 192 kHz.  Needs measure() with lufs on before it.  Returns
+        (int16 [n192, C] at 192 kHz, info).  The filter is the frame-by-frame kernel
+        k_ln_dyn_mc; the host reads pass 1's loudness in between (this
+        path already synchronises in fetch_report)."""
+        s = self._side192()
+        target = float(self.settings["lufs"])
+        d1 = capi.LoudnormDesc(target, LOUDNORM_LRA, LOUDNORM_TP, 0.0, 0.0, 99.0, -70.0, 0.0)
+        self.dyn_filter(d1, stream)
+        self.dyn_measure(stream, lufs_on=True)
+        with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+            i_out = float(s.one.stats[0, 0].item())                 # pass 1's output loudness
+        offset = loudness._fmt(target - i_out)
+        d2 = capi.LoudnormDesc(target, LOUDNORM_LRA, LOUDNORM_TP, float(stats["input_i"]),
+                               float(stats["input_lra"]), float(stats["input_tp"]),
+                               float(stats["input_thresh"]), float(offset))
+        d2.reuse_stream = 1
+        self.dyn_filter(d2, stream)
+        self.dyn_limit(stream)
+        with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+            prof = s.summ.cpu().numpy()
+        info = {"target_offset": offset, "pass1_output_i": i_out, "sample_rate": 192000,
+                "linear_fallback": bool(prof[0] == 1.0)}
+        info["pass2_cycles"] = {k: float(prof[i]) for i, k in enumerate(
+            ("fill", "detect", "envelope", "output", "stats", "r128_out", "detect_calls", "serial_chunks"),
+            start=2)}
+        return s.out[:s.n192], info
+
     def close(self):
         if getattr(self, "_closed", False):
             return
         self._closed = True
         torch.cuda.synchronize(self.device)
+        side = getattr(self, "_s192", None)
+        if side is not None:
+            side.meas.close()
+            side.one.close()
+            self._s192 = None
         self.meas.close()
         self.one.close()
         self.plan.close()
@@ -727,13 +869,14 @@ class MultiChannelJob:
 def delivery_rate(settings, input_rate, channels):
     """The settings key output_rate (amx.settings.output_rate) checked against every rate
     the master of this call can be at: the input's, and 192 kHz when loudnorm may take its
-    dynamic mode (lufs set, at most two channels).  None: deliver the master as it is.
+    dynamic mode (lufs set; at most two channels, or 3..8 with the settings key
+    multichannel_dynamic).  None: deliver the master as it is.
     ValueError for a bad key, or for a pair amx_resample_size refuses (both rates named)."""
     from . import resample
     target = output_rate(settings, input_rate)
     if target is not None:
         ends = [int(input_rate)]
-        if (settings or {}).get("lufs") is not None and int(channels) <= 2:
+        if (settings or {}).get("lufs") is not None and (int(channels) <= 2 or multichannel_dynamic(settings)):
             ends.append(192000)
         for fs in ends:
             resample.check_pair(fs, target)
@@ -758,7 +901,10 @@ def master_array(x, sample_rate, settings, *, quantum=None, seg_frames=128, limi
     any device) -> int16 [frames', 2] CUDA tensor (the 16-bit WAV the reference
     writes) and a report dict.  report["sample_rate"] is the rate of the returned frames:
     the input's, 192000 after loudnorm's dynamic mode, or the settings key output_rate's
-    when it names another (report["resampled_from"] then holds the master's)."""
+    when it names another (report["resampled_from"] then holds the master's).  C = 3..8:
+    int16 [frames', C]; loudnorm's dynamic mode raises DynamicModeUnsupported unless the
+    settings key multichannel_dynamic is True (then MultiChannelJob.dynamic runs it)."""
+    mc_dyn = multichannel_dynamic(settings)                      # a bad key: before any kernel
     x = torch.as_tensor(x)
     if x.dim() == 1:
         x = x.reshape(-1, 1)
@@ -774,8 +920,13 @@ def master_array(x, sample_rate, settings, *, quantum=None, seg_frames=128, limi
         job = MultiChannelJob(sample_rate, x.shape[1], settings, x.shape[0], quantum=quantum,
                               input_s16=s16, seg_frames=seg_frames)
         y = job.run(x)
-        job.fetch_report(raise_dynamic=True)
+        rep = job.fetch_report(raise_dynamic=not mc_dyn)
         job.report.update(sample_rate=job.fs, job=job)
+        if rep["modes"] and rep["modes"][0] == "dynamic":
+            # (multichannel_dynamic) :240 in dynamic mode: the 192 kHz path replaces the
+            # linear step's output, as below for stereo
+            y, info = job.dynamic(rep["stats"][0])
+            job.report.update(dynamic=info, sample_rate=info["sample_rate"])
         return deliver(y, job.report, target), job.report
     job = MasteringJob(sample_rate, x.shape[1], settings, [x.shape[0]], quantum=quantum,
                        input_s16=s16, seg_frames=seg_frames, limiter_seg_frames=limiter_seg_frames,

@@ -57,6 +57,19 @@ def output_rate(settings, input_rate):
     raise ValueError("output_rate must be a positive int (Hz), \"input\" or None, not %r" % (rate,))
 
 
+def multichannel_dynamic(settings):
+    """the optional settings key multichannel_dynamic: True runs loudnorm's dynamic mode on
+    3..8-channel tracks (DESIGN.md 3.9: a 192 kHz master where the linear conditions fail);
+    False or absent keeps DynamicModeUnsupported / `Error: ...` for them.  ValueError for
+    anything that is not a bool (1, "yes", None)."""
+    if not settings or "multichannel_dynamic" not in settings:
+        return False
+    on = settings["multichannel_dynamic"]
+    if not isinstance(on, bool):
+        raise ValueError("multichannel_dynamic must be True or False, not %r" % (on,))
+    return on
+
+
 def apply_preset(settings, preset_name):
     """mastering_gui.py:165-168: a preset sets the four EQ gains ("None" zeroes them)."""
     s = dict(settings)

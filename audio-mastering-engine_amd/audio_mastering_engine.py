@@ -12,6 +12,9 @@ Mirrors audio_mastering_engine.py's call surface for the hot path:
   The optional key ``flac_decode`` says where a ``*.flac`` input is decoded: ``"host"``
   (absent: the host decoder and an upload of the decoded samples) or ``"device"`` (the
   file's bytes go up and are decoded there); any other value is a ``ValueError``.
+  The optional key ``multichannel_dynamic`` (a bool, absent: ``False``) lets a file with 3
+  to 8 channels take loudnorm's dynamic mode (a 192 kHz master, like a stereo file's)
+  where it otherwise ends in ``DynamicModeUnsupported``; any other value is a ``ValueError``.
 * ``process_audio_with_ffmpeg_pipeline`` -- alias of ``master_audio``.
 * ``process_audio(settings, status_cb, progress_cb, art_cb, tag_cb)`` -- the GUI
   wrapper (:94-137): mastering, the optional MP3 export (:97-98, ``export_to_mp3``
@@ -41,7 +44,7 @@ import numpy as np  # noqa: E402
 
 from amx import wavio  # noqa: E402
 from amx.chunking import bounds_for  # noqa: E402
-from amx.settings import EQ_PRESETS, flac_decode_mode, output_rate  # noqa: E402,F401
+from amx.settings import EQ_PRESETS, flac_decode_mode, multichannel_dynamic, output_rate  # noqa: E402,F401
 
 __all__ = ["master_audio", "process_audio", "process_audio_with_ffmpeg_pipeline", "EQ_PRESETS",
            "master_array", "export_to_mp3"]
@@ -137,6 +140,20 @@ def _normalize(job):
     return None
 
 
+def _normalize_multichannel(job):
+    """_normalize for a MultiChannelJob (settings key multichannel_dynamic): the
+    measurement and decision; dynamic mode returns MultiChannelJob.dynamic's (output, info),
+    linear mode and the -inf skip None"""
+    job.measure(lufs_on=True)
+    report = job.fetch_report(raise_dynamic=False)
+    mode = report["modes"][0] if report["modes"] else "off"
+    if mode == "skip":
+        logging.warning("Measured loudness is -inf (silent audio). Skipping normalization.")
+    if mode == "dynamic":
+        return job.dynamic(report["stats"][0])
+    return None
+
+
 def master_audio(settings, status_callback=None, progress_callback=None):
     import torch
     from amx.engine import MasteringJob
@@ -148,6 +165,7 @@ def master_audio(settings, status_callback=None, progress_callback=None):
         raise ValueError("Input or output file not specified.")              # :173
     flac_decode_mode(settings)                         # a bad flac_decode: before any file is read
     output_rate(settings, 0)                           # a bad output_rate likewise
+    multichannel_dynamic(settings)                     # and a bad multichannel_dynamic
     from amx.engine import delivery_rate, deliver
     # a master rate the resampler cannot take to output_rate: before any kernel runs
     check = lambda rate, channels: delivery_rate(settings, rate, channels)   # noqa: E731
@@ -217,8 +235,11 @@ def _master_multichannel(settings, status, progress, d_in, fs, frames, channels,
     """master_audio for a file with 3..8 channels: the chain over the interleaved stream
     (:252), the measurement over the C channels and the C-channel alimiter
     (amx.engine.MultiChannelJob), with the same status strings and progress sequence.
-    Loudnorm's dynamic mode is not run for such a file (DynamicModeUnsupported).  target:
-    the delivery rate (settings key output_rate), None: the file's own."""
+    Loudnorm's dynamic mode raises DynamicModeUnsupported for such a file unless the
+    settings key multichannel_dynamic is True: then MultiChannelJob.dynamic runs it (the
+    master is at 192 kHz), and -- as for stereo, :243-246 -- an error in the loudness stage
+    is logged and the track finalised without the gain.  target: the delivery rate
+    (settings key output_rate), None: the master's own."""
     import torch
     from amx.engine import MultiChannelJob, deliver
     num_chunks = len(bounds)
@@ -233,19 +254,36 @@ def _master_multichannel(settings, status, progress, d_in, fs, frames, channels,
     status("Re-assembling processed chunks with concat filter...")           # :205
     progress(num_chunks + 1, total_steps)                                     # :206
     status("Concatenation complete.")                                         # :213
+    dyn = None
     if settings.get("lufs") is not None:                                      # :216
         status("Normalizing final loudness...")                               # :217
         progress(num_chunks + 2, total_steps)                                 # :218
-        job.measure(lufs_on=True)
-        rep = job.fetch_report(raise_dynamic=True)
-        if rep["modes"] and rep["modes"][0] == "skip":
-            logging.warning("Measured loudness is -inf (silent audio). Skipping normalization.")
+        if multichannel_dynamic(settings):
+            try:
+                dyn = _normalize_multichannel(job)
+            except Exception as e:                                            # :243-246
+                logging.exception("Error during disk-based normalization.")
+                if isinstance(e, subprocess.CalledProcessError):
+                    logging.error(f"FFMPEG STDERR:\n{e.stderr}")
+                dyn = None
+                job.measure(lufs_on=False)
+        else:
+            job.measure(lufs_on=True)
+            rep = job.fetch_report(raise_dynamic=True)
+            if rep["modes"] and rep["modes"][0] == "skip":
+                logging.warning("Measured loudness is -inf (silent audio). Skipping normalization.")
     else:
         job.measure(lufs_on=False)
     status("Applying final limiting and exporting...")                        # :221
     progress(num_chunks + 3, total_steps)                                     # :222
-    rate = {"sample_rate": fs}
-    y = deliver(job.finalize(), rate, target)
+    if dyn is None:
+        rate = {"sample_rate": fs}
+        y = job.finalize()
+    else:
+        # the alimiter ran on the 192 kHz file inside dynamic() (:223 keeps its rate)
+        rate = {"sample_rate": dyn[1]["sample_rate"]}
+        y = dyn[0]
+    y = deliver(y, rate, target)
     _write_output(output_file, y, rate["sample_rate"], settings)
     progress(total_steps, total_steps)                                        # :224
     logging.info(f"Finished GPU pipeline, exported to {output_file}")

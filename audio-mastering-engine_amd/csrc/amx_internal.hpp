@@ -268,6 +268,29 @@ hipError_t launch_loudnorm(const LnArgs &a, const LpArgs &p, const uint32_t *x, 
 hipError_t launch_loudnorm_shard(const LnArgs &a, const LpArgs &p, const uint32_t *x, int64_t n_in,
                                  const SwrDev &r, int64_t u_lo, int64_t u_hi, int64_t y_lo, int64_t y_hi, int part,
                                  bool resample, hipStream_t st);
+// the upsample step alone: [j0, j1) of the 192 kHz stream of one stereo s16 plane into u
+hipError_t launch_ln_upsample(const uint32_t *x, int64_t n_in, const SwrDev &r, int64_t j0, int64_t j1, float *u,
+                              const int32_t *gate, hipStream_t st);
+// af_loudnorm's 192 kHz modes on one whole track of C = 3..8 channels, frame by frame
+// (amx_mc_loudnorm.hip k_ln_dyn_mc<C>)
+struct LnMcArgs {
+    int64_t n192;                 // 192 kHz frames
+    const float *u;               // [P][n192][2] the channel pairs' resampled streams, P = (C + 1) / 2:
+                                  // channel c is lane c & 1 of plane c >> 1
+    int64_t plane;                // floats from one plane to the next
+    double *ring;                 // limiter ring [40320][C] + C doubles of slack (scratch)
+    int16_t *y;                   // [n192][C] output
+    double *summary;              // [16] as LnArgs::summary
+    const double *hops;           // [>= n192 / 19200 + 1][2] the combined hop energies (lane 1: 0)
+    const double *peak;           // [2] the largest channel's 192 kHz sample peak (both lanes)
+    const double *energies, *bounds;
+    double target_i, target_lra, target_tp;       // target_tp linear (the ceiling)
+    double measured_i, measured_thresh, offset;   // offset linear
+    double weights[21];           // init_gaussian_filter
+    double kb[5], ka[5];          // libebur128 K filter at 192 kHz (direct form)
+};
+#define AMX_LN_MC_RING(C) ((int64_t)(C) * AMX_LN_RING + 64)   // doubles: the ring and its slack (>= C)
+hipError_t launch_mc_loudnorm(const LnMcArgs &a, int C, hipStream_t st);
 #define AMX_LN_GATED(g) ((g) && (((g)[0] >> 4) & 15) != 3)   // k_decide mode 3 = dynamic
 hipError_t launch_up1(const UpArgs &a, hipStream_t st, hipStream_t aux, hipEvent_t fork, hipEvent_t join);
 hipError_t launch_up2(const UpArgs &a, hipStream_t st);

@@ -18,6 +18,7 @@
 // (float32 input normally skips this kernel: k_front1s quantises it in the chain's
 // first pass.)  One thread per frame, grid-stride; a memory-bound pass.
 #include "amx_dev.hpp"
+#include "amx_ln_dev.hpp"
 
 namespace amx {
 
@@ -171,14 +172,7 @@ __global__ void __launch_bounds__(256) k_mc_split_pairs(const int16_t *__restric
         reinterpret_cast<uint32_t *>(pairs)[q] = pack2(l, r);
     }
 }
-// libebur128's default channel map (ebur128_init_channel_map): 4 channels L R Ls Rs, 5
-// L R C Ls Rs, otherwise L R C unused Ls Rs, later channels unused; the surrounds
-// (Mp110 / Mm110) weigh 1.41 (ebur128_calc_gating_block)
-__device__ __forceinline__ double ebur_weight(int C, int c) {
-    if (C == 4) return c < 2 ? 1.0 : 1.41;
-    if (C == 5) return c < 3 ? 1.0 : 1.41;
-    return c < 3 ? 1.0 : (c == 3 ? 0.0 : (c < 6 ? 1.41 : 0.0));
-}
+// the channels' hop energies with libebur128's channel weights (ebur_weight, amx_ln_dev.hpp)
 __global__ void __launch_bounds__(256) k_mc_loudness_combine(const double *__restrict__ hops, int64_t max_hops,
                                                              const double *__restrict__ peak, int C,
                                                              double *__restrict__ hops1, double *__restrict__ peak1) {

@@ -445,6 +445,21 @@ int64_t ln_seg_base(const LnLayout &lo, int64_t n192, int k) {
     const int64_t S0 = n192 - (LN_FIRST_FRAMES - 19200);
     return phi <= lo.T ? (int64_t)19200 * phi : S0 + (int64_t)19200 * (phi - lo.T - 1);
 }
+// af_loudnorm's init_gaussian_filter: the 21 weights of its gain smoothing
+void ln_gaussian_weights(double *weights) {
+    double total = 0.0;
+    const double sigma = 3.5;
+    const int off = 21 / 2;
+    const double c1 = 1.0 / (sigma * std::sqrt(2.0 * M_PI));
+    const double c2 = 2.0 * std::pow(sigma, 2.0);
+    for (int i = 0; i < 21; i++) {
+        const int x = i - off;
+        weights[i] = c1 * std::exp(-(std::pow(x, 2.0) / c2));
+        total += weights[i];
+    }
+    const double adjust = 1.0 / total;
+    for (int i = 0; i < 21; i++) weights[i] *= adjust;
+}
 int check_edges(const amx_plan *p, const int16_t *d_edge) {
     if (!p->resamp || d_edge) return AMX_OK;
     for (const SpanDev &sp : p->spans)
@@ -559,20 +574,7 @@ int ln_args(amx_plan *p, int32_t track, const amx_loudnorm_desc *d, const double
     a.measured_i = d->measured_i;
     a.measured_thresh = d->measured_thresh;
     a.offset = std::pow(10., d->offset / 20.);
-    {   // init_gaussian_filter
-        double total = 0.0;
-        const double sigma = 3.5;
-        const int off = 21 / 2;
-        const double c1 = 1.0 / (sigma * std::sqrt(2.0 * M_PI));
-        const double c2 = 2.0 * std::pow(sigma, 2.0);
-        for (int i = 0; i < 21; i++) {
-            const int x = i - off;
-            a.weights[i] = c1 * std::exp(-(std::pow(x, 2.0) / c2));
-            total += a.weights[i];
-        }
-        const double adjust = 1.0 / total;
-        for (int i = 0; i < 21; i++) a.weights[i] *= adjust;
-    }
+    ln_gaussian_weights(a.weights);
     for (int k = 0; k < 5; k++) { a.kb[k] = p->kdf_b[k]; a.ka[k] = p->kdf_a[k]; }
     q = amx::LpArgs{};
     q.n = n192;
@@ -1320,6 +1322,82 @@ int amx_mc_limiter_out(const amx_plan *p, const amx_final_desc *fd, const int16_
     const double level = fd->auto_level ? 1 / fd->limit : 1;
     HIPCHK(amx::launch_mc_limiter_out(d_y, p->out_frames, channels, halo, d_gains, d_ctl, d_att, fd->level_in,
                                       level, fd->level_out, fd->limit, d_out, (hipStream_t)stream));
+    return AMX_OK;
+}
+
+}  // extern "C"
+
+namespace {
+// amx_mc_loudnorm_192k's plan: ceil(C / 2) equal whole tracks (the channel pairs); *n192
+// the 192 kHz frames of each (AMX_ERANGE as ln_frames)
+int ln_mc_frames(const amx_plan *p, int32_t channels, int64_t *n192) {
+    if (channels < 3 || channels > 8) return fail(AMX_EINVAL, "%d channels (3..8; 1 or 2: amx_loudnorm_192k)", channels);
+    const int P = (channels + 1) / 2;
+    if (p->n_tracks != P) return fail(AMX_EINVAL, "the pairs' plan holds %d tracks, %d channels need %d", p->n_tracks, channels, P);
+    for (int t = 0; t < P; t++) {
+        const SpanDev &sp = p->spans[t];
+        if (sp.tframe0 != 0 || sp.ttotal != sp.out_n || sp.out_n != p->spans[0].out_n)
+            return fail(AMX_EINVAL, "the pairs' plan holds one whole track of the same length per channel pair");
+    }
+    return ln_frames(p, 0, n192);
+}
+int64_t ln_mc_plane_bytes(int64_t n192) { return ((n192 * 2 * (int64_t)sizeof(float) + 255) / 256) * 256; }
+}  // namespace
+
+extern "C" {
+
+int amx_mc_loudnorm_192k_size(const amx_plan *p, int32_t channels, int64_t *frames, int64_t *ws_bytes) {
+    if (!p || !frames || !ws_bytes) return fail(AMX_EINVAL, "null argument");
+    int64_t n192 = 0;
+    if (int rc = ln_mc_frames(p, channels, &n192)) return rc;
+    *frames = n192;
+    *ws_bytes = ((channels + 1) / 2) * ln_mc_plane_bytes(n192) + AMX_LN_MC_RING(channels) * (int64_t)sizeof(double);
+    return AMX_OK;
+}
+
+int amx_mc_loudnorm_192k(amx_plan *p, int32_t channels, const amx_loudnorm_desc *d, const int16_t *d_pairs,
+                         const double *d_hops1, int64_t max_hops, const double *d_peak1, int16_t *d_y192,
+                         double *d_summary, void *d_ws, void *stream) {
+    if (!p || !d || !d_pairs || !d_hops1 || !d_peak1 || !d_y192 || !d_summary || !d_ws)
+        return fail(AMX_EINVAL, "null argument");
+    int64_t n192 = 0;
+    if (int rc = ln_mc_frames(p, channels, &n192)) return rc;
+    if (max_hops < n192 / 19200 + 1) return fail(AMX_EINVAL, "d_hops1 holds %lld hops", (long long)max_hops);
+    if (n192 <= 0) return AMX_OK;
+    const int P = (channels + 1) / 2;
+    const int64_t plane = ln_mc_plane_bytes(n192);
+    char *w = reinterpret_cast<char *>(d_ws);
+    amx::LnMcArgs a{};
+    a.n192 = n192;
+    a.u = reinterpret_cast<const float *>(w);
+    a.plane = plane / (int64_t)sizeof(float);
+    a.ring = reinterpret_cast<double *>(w + (int64_t)P * plane);
+    a.y = d_y192;
+    a.summary = d_summary;
+    a.hops = d_hops1;
+    a.peak = d_peak1;
+    a.energies = p->d_energies;
+    a.bounds = p->d_bounds;
+    // af_loudnorm init / config_input: dB options to the linear factors it keeps
+    a.target_i = d->target_i;
+    a.target_lra = d->target_lra;
+    a.target_tp = std::pow(10., d->target_tp / 20.);
+    a.measured_i = d->measured_i;
+    a.measured_thresh = d->measured_thresh;
+    a.offset = std::pow(10., d->offset / 20.);
+    ln_gaussian_weights(a.weights);
+    for (int k = 0; k < 5; k++) { a.kb[k] = p->kdf_b[k]; a.ka[k] = p->kdf_a[k]; }
+    hipStream_t st = (hipStream_t)stream;
+    if (d->reuse_stream == 0) {
+        // each channel pair through the stereo upsampler into its plane
+        amx::SwrDev r{p->up_pc, p->up_lin, p->up_src, p->up_dst, p->d_bank, p->up_taps, p->up_alloc};
+        for (int t = 0; t < P; t++) {
+            const SpanDev &sp = p->spans[t];
+            HIPCHK(amx::launch_ln_upsample(reinterpret_cast<const uint32_t *>(d_pairs) + sp.out_off, sp.out_n, r, 0,
+                                           n192, reinterpret_cast<float *>(w + (int64_t)t * plane), nullptr, st));
+        }
+    }
+    HIPCHK(amx::launch_mc_loudnorm(a, channels, st));
     return AMX_OK;
 }
 

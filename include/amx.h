@@ -56,7 +56,9 @@ extern "C" {
  * 6 (unchanged): amx_flac_scan and amx_flac_decode_device added (FLAC input decoded on the
  * device) with their two structures and AMX_EUNSUPPORTED; nothing that existed changed.
  * 6 (unchanged): amx_resample_size, amx_resampler_create / _run / _free added (the master
- * at a chosen sample rate); nothing that existed changed. */
+ * at a chosen sample rate); nothing that existed changed.
+ * 6 (unchanged): amx_mc_loudnorm_192k_size and amx_mc_loudnorm_192k added (loudnorm's
+ * 192 kHz modes on 3..8 channels); nothing that existed changed. */
 #define AMX_ABI_VERSION 6
 
 #if defined(__GNUC__)
@@ -638,6 +640,24 @@ AMX_API int amx_mc_peak_pick(const int16_t *d_y, int64_t frames, int32_t channel
 AMX_API int amx_mc_limiter_out(const amx_plan *plan, const amx_final_desc *fd, const int16_t *d_y,
                                int32_t channels, const double *d_gains, const int32_t *d_ctl,
                                const double *d_att, int16_t *d_out, void *stream);
+/* (ABI 6, added without a layout change) af_loudnorm's 192 kHz modes (dynamic, or the
+ * < 3 s linear fallback) on one track of channels = 3..8, frame by frame on one workgroup
+ * (DESIGN.md 3.9).  pairs_plan: the stereo measure plan whose ceil(C/2) equal whole tracks
+ * hold the channel pairs (amx_mc_split_pairs), d_pairs its `out`.  d_hops1 [max_hops][2] /
+ * d_peak1 [4]: the track's combined hop energies and peaks (amx_mc_loudness_combine).
+ * desc: the options and pass 2's measured values / offset as host numbers; reuse_stream
+ * 1: d_ws still holds the 192 kHz planes of the previous call on the same d_pairs.
+ * d_y192 int16 [frames][channels]; d_summary [16] as amx_loudnorm_192k's.  _size gives the
+ * 192 kHz frames and d_ws's bytes; AMX_ERANGE where amx_loudnorm_192k_size gives it.
+ * Validates everything before any launch (AMX_EINVAL: channels outside 3..8, a null
+ * pointer, max_hops < frames / 19200 + 1, a plan that does not hold ceil(C/2) equal whole
+ * tracks); never allocates or synchronises; an empty track launches nothing. */
+AMX_API int amx_mc_loudnorm_192k_size(const amx_plan *pairs_plan, int32_t channels, int64_t *frames,
+                                      int64_t *ws_bytes);
+AMX_API int amx_mc_loudnorm_192k(amx_plan *pairs_plan, int32_t channels, const amx_loudnorm_desc *desc,
+                                 const int16_t *d_pairs, const double *d_hops1, int64_t max_hops,
+                                 const double *d_peak1, int16_t *d_y192, double *d_summary, void *d_ws,
+                                 void *stream);
 
 /* ---------------------------------------------------------------------------------
  * (ABI 6, added without a layout change) The finished master at another sample rate
