@@ -103,4 +103,14 @@ def chain_desc(fs, channels_in, settings):
                 raise TypeError("multiband requires %s_thresh and %s_ratio" % (band, band))
             d.comp_threshold_db[i] = float(t)
             d.comp_ratio[i] = float(r)
+        # max_attenuation(rms) tables given instead of computed (amx_chain_desc.comp_m_table):
+        # like _env_warm, a key for the tests (the plan's division form depends on the values)
+        tabs = settings.get("_comp_m_table")
+        if tabs is not None:
+            for i, t in enumerate(tabs):
+                t = np.ascontiguousarray(t, np.float64)
+                if t.shape != (32769,):
+                    raise ValueError("_comp_m_table: three arrays of 32769 values")
+                keep.append(t)
+                d.comp_m_table[i] = t.ctypes.data_as(capi.c_double_p)
     return d, keep

@@ -253,6 +253,16 @@ class MasteringJob:
         keys = ("reruns", "max_chain", "chains", "wide")
         return [dict(zip(keys, r)) for r in rows if any(r)]
 
+    def env_rcp(self):
+        """The plan's envelope division form (amx_env_counters' word after the counters):
+        1 = reciprocal multiply + FMA residual, 0 = plain division (the plan's check of
+        the former failed for some table value)."""
+        import ctypes
+        n = 16 * 4 + 1
+        buf = (ctypes.c_int32 * n)()
+        capi.check(capi.load().amx_env_counters(self.plan.h, capi.ptr(self.ws), buf, n), "amx_env_counters")
+        return int(buf[n - 1])
+
     # --------------------------------------------- loudnorm dynamic mode (192 kHz)
     def _job192(self, t, cached=True):
         """the 192 kHz side of track t: a measure-only plan at 192 kHz holding the

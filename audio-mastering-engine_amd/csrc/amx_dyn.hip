@@ -46,8 +46,7 @@ typedef uint32_t u4v __attribute__((ext_vector_type(4)));
 // Frames before the chunk count as 0 (audioop.rms over the shorter window divides by
 // the frames present).  Loads are 16-B vectors (the LDS origin is 16-frame aligned);
 // the output is r_i itself (u16, clamped to 32768 = |sample| max), m is not formed here.
-#define AMX_RMS_N 4096
-#define AMX_RMS_MAXLOOK 1024
+#define AMX_RMS_N 4096   // (AMX_RMS_MAXLOOK, amx_tables.hpp: the plan refuses a longer window)
 
 // LDS index of prefix slot k: one spare slot per 16 keeps the scan's stores (lane
 // stride 17 slots, odd) on distinct bank pairs
@@ -830,7 +829,14 @@ __global__ void __launch_bounds__(64) k_envchain(const ChainDev *__restrict__ cd
                     done = true;
                     break;
                 }
-                if (ss == r) { done = true; break; }         // the link holds: the rest stands
+                if (ss == r) {                               // the link holds: the rest stands,
+                    // unless the link was broken when the heads were marked (the end changed
+                    // onto a start that already had this value): the segments after it then
+                    // had a broken predecessor, so a broken link among them has no head
+                    stale = stale || !(r == old_end);
+                    done = true;
+                    break;
+                }
                 state = r;                                   // an active segment to re-run
                 cur = nx + f;
                 sg = et[cur];

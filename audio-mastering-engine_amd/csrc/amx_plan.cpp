@@ -878,7 +878,10 @@ int amx_env_counters(const amx_plan *p, const void *d_ws, int32_t *out, int32_t 
     if (!p || !out || n < 0) return fail(AMX_EINVAL, "null argument");
     const int32_t have = AMX_ENV_MAX_ROUNDS * AMX_ENV_NCTR;
     for (int32_t i = 0; i < n; i++) out[i] = 0;
-    if (!p->mb || p->n_es == 0) return AMX_OK;
+    if (!p->mb) return AMX_OK;
+    // the word after the counters: the plan's division form (ChainDev::env_rcp; a host value)
+    if (n > have) out[have] = p->cd.env_rcp;
+    if (p->n_es == 0) return AMX_OK;
     if (!d_ws) return fail(AMX_EINVAL, "null workspace");
     const int32_t k = n < have ? n : have;
     HIPCHK(hipMemcpy(out, reinterpret_cast<const char *>(d_ws) + p->o_eflags + AMX_ENV_MAX_ROUNDS * 4,

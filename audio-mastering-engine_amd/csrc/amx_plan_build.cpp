@@ -455,6 +455,10 @@ int Builder::chain_coefficients() {
         cd.xhi[k] = desc->xover_hi_sos[k];
     }
     cd.look = (int32_t)(5.0 * (fs / 1000.0));
+    // the detector's window must fit k_rms's largest prefix-sum tile (amx_dyn.hip)
+    if (p->mb && cd.look > AMX_RMS_MAXLOOK)
+        return fail(AMX_ERANGE, "multiband: the %d-frame detector window at %d Hz exceeds %d frames (rates up to %d Hz)",
+                    cd.look, fs, AMX_RMS_MAXLOOK, AMX_RMS_MAXLOOK * 200);
     return AMX_OK;
 }
 

@@ -14,6 +14,7 @@
 #define AMX_ENV_NCTR 4         // fix-up diagnostic counters per round (after the flags; k_envchain)
 #define AMX_ENV_BACT (AMX_ENV_MAX_ROUNDS * (1 + AMX_ENV_NCTR))  // band-activity words after the counters
 #define AMX_ENV_LIST (AMX_ENV_BACT + 4)  // re-run list length, chain-head list length, k_envseq's flag
+#define AMX_RMS_MAXLOOK 1024   // the compressor detector's longest window (k_rms<1024>): rates to 204.8 kHz
 #define AMX_EQC 64        // compact EQ coefficient block (see ChainDev::eqc)
 #define AMX_MEAS_RATE 192000  // loudnorm pass 1 measures at 192 kHz (af_loudnorm dynamic mode)
 #define AMX_SWR_MAX_ALLOC 144   // the widest resampler row (filter_alloc) restated

@@ -357,8 +357,11 @@ AMX_API int amx_flac_encode_ex(const int16_t *d_pcm, int64_t frames, int32_t cha
 /* Diagnostics of the compressor envelope's fix-up (AMX_STAGE_FIX) of the last step run
  * on d_ws: out[0..3] = segments the chain walkers re-ran, the longest walk (segments one
  * wave re-ran in turn), chains, and segments of the optimistic parallel pass before them
- * (out[4..] are 0).  Synchronous (hipMemcpy): call it outside graph capture.  Replaces no
- * reference line. */
+ * (out[4..] are 0).  out[64], where n reaches it, is a plan value, not a counter: 1 when
+ * the envelope divides by reciprocal multiply + FMA residual, 0 when the plan's check of
+ * that form failed and the kernels divide (d_ws may be NULL for it alone when the plan has
+ * no envelope segments).  Synchronous (hipMemcpy): call it outside graph capture.
+ * Replaces no reference line. */
 AMX_API int amx_env_counters(const amx_plan *plan, const void *d_ws, int32_t *out, int32_t n);
 
 /* Gate a plan's per-sample kernels on a device word: with d_gate set, the K-weighting

@@ -134,9 +134,11 @@ std::vector<Case> cases() {
     // one (24 kHz), the 1024-phase interpolating rates, a downsampling rate (> 32 taps), and
     // rates the resampler restatement refuses (the measurement at the track's own rate)
     const int rates[] = {48000, 96000, 192000, 44100, 88200, 176400, 32000, 64000, 24000, 22050, 11025, 384000,
-                         200001};
+                         200001, 352800};
     for (int fs : rates) add("rate_" + std::to_string(fs), desc_eq(fs), TWO);
-    for (int fs : {48000, 96000, 192000, 44100, 22050, 384000}) add("mb_" + std::to_string(fs), desc_eq(fs, 1), TWO);
+    // (above 204.8 kHz the compressor's detector window passes k_rms's tile: AMX_ERANGE)
+    for (int fs : {48000, 96000, 192000, 44100, 22050, 384000, 352800})
+        add("mb_" + std::to_string(fs), desc_eq(fs, 1), TWO);
     // multiband on few CUs over ~200 k frames: Le grows past its floor, the Le_t tables differ
     const std::vector<amx_chunk> big = chunks({{0, 0, 100000}, {0, 100000, 70001}, {1, 170001, 30000}});
     add("mb_ncu4", desc_eq(44100, 1), big).ncu = 4;

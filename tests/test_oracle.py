@@ -133,6 +133,33 @@ def test_compressor_matches_pydub_restatement(oracle_mod):
         np.testing.assert_array_equal(oracle_mod.compress(x, fs, thr, ratio), ref)
 
 
+def test_compressor_edges_match_pydub_restatement(oracle_mod):
+    """C compressor == the pydub 0.25.1 restatement on the ground tests/test_gpu_compressor.py
+    holds the device to: the crafted signals of tests/compressor_signals.py as band inputs
+    (``step`` rotated to start on its plateau, so frame 0 has energy), five rates
+    (fractional and whole attack frame counts, each detector window form), and twelve
+    (threshold, ratio) pairs including ratios below 1, negative, and thresholds above 0 dBFS."""
+    import sys
+    sys.path.insert(0, GOLDEN)
+    import pydub_restated as P
+    from compressor_signals import PAIRS, SIGNALS, edge_signal
+    cases = 0
+    for fs in (11025, 44100, 48000, 96000, 192000):
+        n = 1300 if fs > 50000 else 700
+        for name in SIGNALS:
+            x = edge_signal(name, [n], fs, seed=5)
+            if name == "step":
+                x = np.concatenate([x[n // 3:], x[:n // 3]])       # starts on the step
+            seg = P.AudioSegment(data=x.tobytes(), sample_width=2, frame_rate=fs, channels=2)
+            for thr, ratio in PAIRS:
+                ref = np.frombuffer(P.compress_dynamic_range(seg, thr, ratio)._data, np.int16).reshape(-1, 2)
+                got = oracle_mod.compress(x, fs, thr, ratio)
+                assert np.array_equal(got, ref), "%s fs %d (%g, %g): %d samples differ" % (
+                    name, fs, thr, ratio, int((got != ref).sum()))
+                cases += 1
+    assert cases == 5 * 8 * 12
+
+
 def test_overlay_lengths(oracle_mod):
     """pydub ms rounding (SURVEY.md A.10 examples)."""
     assert oracle_mod.overlay_len(1234567, 48000) == 1234560

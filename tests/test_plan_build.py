@@ -77,9 +77,23 @@ def test_tables_equal_the_recorded_plan(harness_output):
         want = _cases(f.read())
     got = _cases(harness_output.stdout)
     assert sorted(k for k in got if k) == sorted(k for k in want if k)
-    assert len([k for k in want if k]) == 85      # a truncated golden would pass the loop below
+    assert len([k for k in want if k]) == 87      # a truncated golden would pass the loop below
     for name in want:
         assert got[name] == want[name], name
+
+
+def test_multiband_refused_above_204800_hz(harness_output):
+    """the compressor's detector window (5 ms) must fit k_rms's largest tile (1024 frames):
+    352.8 and 384 kHz with multiband fail at plan construction with AMX_ERANGE and a message
+    naming the limit -- in the host-only builder, where nothing can have been launched --
+    and the same rates without multiband build"""
+    got = _cases(harness_output.stdout)
+    for fs, look in ((352800, 1764), (384000, 1920)):
+        lines = got["mb_%d" % fs]
+        assert len(lines) == 1 and lines[0].startswith("rc=-4 err=multiband: the %d-frame" % look), lines
+        assert "1024 frames" in lines[0] and "204800 Hz" in lines[0], lines
+        assert got["rate_%d" % fs][0] == "rc=0 err=" and got["rate_%d" % fs][-1].endswith("inv ok")
+    assert got["mb_192000"][0] == "rc=0 err="
 
 
 def test_invariants_hold(harness_output):
