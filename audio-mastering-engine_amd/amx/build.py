@@ -21,7 +21,7 @@ CSRC = os.path.join(PKG, "csrc")
 OUT = os.path.join(PKG, "lib", "libamx.so")
 HEADER = os.path.join(PKG, "..", "include", "amx.h")
 SOURCES = ["amx_chain.hip", "amx_scan.hip", "amx_dyn.hip", "amx_loud.hip", "amx_loud192.hip", "amx_final.hip", "amx_io.hip",
-           "amx_loudnorm.hip", "amx_mc_loudnorm.hip", "amx_flacenc.hip", "amx_flacdec.hip", "amx_resample.hip",
+           "amx_loudnorm.hip", "amx_ln_dyn.hip", "amx_flacenc.hip", "amx_flacdec.hip", "amx_resample.hip",
            "amx_plan.cpp", "amx_plan_build.cpp", "amx_flac.cpp"]
 HEADERS = ["amx_internal.hpp", "amx_dev.hpp", "amx_tables.hpp", "amx_plan_build.hpp", "amx_plan.hpp",
            "amx_flacdec_core.hpp", "amx_ln_dev.hpp"]

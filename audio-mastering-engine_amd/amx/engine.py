@@ -75,6 +75,11 @@ def wait_host_word(ready, what, timeout_s=None):
                                "collective?)" % (what, timeout_s))
 
 
+def on_stream(stream):
+    """torch's stream context for `stream` (None: the current stream)"""
+    return torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream())
+
+
 class MasteringJob:
     def __init__(self, sample_rate, channels_in, settings, track_frames, *, quantum=None,
                  input_s16=False, seg_frames=128, device=None, chunks=None, track_frame0=None,
@@ -333,7 +338,7 @@ class MasteringJob:
             job2.histograms(stream)
             job2.dd.lufs_on = 1
             job2.decide(stream)
-            with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+            with on_stream(stream):
                 self._i_out[t:t + 1].copy_(job2.stats[0, 0:1])       # pass 1's output loudness
         self.timed("ln_measure1", measure1, stream)
         d2 = capi.LoudnormDesc(target, LOUDNORM_LRA, LOUDNORM_TP, 0.0, 0.0, 99.0, -70.0, 0.0)
@@ -347,7 +352,7 @@ class MasteringJob:
             # (a track under 3 s takes the unlimited linear path: measured)
             bound = ln_output_bound(n192)
             if bound is not None:
-                with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+                with on_stream(stream):
                     job2.peak.fill_(bound)
             else:
                 job2.loudness_pass1(stream, tail=False)
@@ -358,7 +363,7 @@ class MasteringJob:
         return {"t": t, "n192": n192, "job2": job2, "ws2": ws2, "summ": summ}
 
     def _dyn_result(self, run, stream):
-        with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+        with on_stream(stream):
             prof = run["summ"].cpu().numpy()
             i_out = float(self._i_out[run["t"]].item())
         target = float(self.settings["lufs"])
@@ -602,6 +607,67 @@ class MasteringJob:
         return self.y[s.out_offset:s.out_offset + s.out_frames]
 
 
+class McStages:
+    """The measure and limit stages of one C-channel track (3..8 channels) at one rate;
+    MultiChannelJob holds one set at the input rate and, for dynamic mode, one at 192 kHz.
+    meas: a measure plan with the track's P = ceil(C / 2) channel pairs as stereo tracks;
+    one: a one-track plan that takes their combined loudness, decides, and runs the
+    alimiter on the per-frame peak signal, leaving its attenuation in att."""
+
+    def __init__(self, fs, C, frames, lufs, limiter, seg_frames, device):
+        self.C = C
+        m = max(1, int(frames))
+        P = (C + 1) // 2
+        self.meas = MasteringJob(fs, 2, {"lufs": lufs}, [m] * P, input_s16=True,
+                                 chunks=[(p, p * m, m) for p in range(P)], device=device, measure_only=True,
+                                 seg_frames=seg_frames, limiter=limiter)
+        self.one = MasteringJob(fs, 2, {"lufs": lufs}, [m], input_s16=True, chunks=[(0, 0, m)], device=device,
+                                measure_only=True, seg_frames=seg_frames, limiter=limiter)
+        assert self.meas.max_hops == self.one.max_hops
+        self.att = torch.ones(m, dtype=torch.float64, device=device)
+        capi.check(capi.load().amx_plan_set_limiter_trace(self.one.plan.h, capi.ptr(self.att)),
+                   "amx_plan_set_limiter_trace")
+        # af_alimiter's attack slope is / (C B) * C: the peak signal's stereo run takes C there
+        capi.check(capi.load().amx_plan_set_limiter_channels(self.one.plan.h, C),
+                   "amx_plan_set_limiter_channels")
+
+    def measure(self, src, n, stream, lufs_on):
+        """loudnorm's measurement of src int16 [n, C]: every channel's 192 kHz K-weighted
+        hop energies and peaks (the pairs as tracks), combined with the channel weights
+        into the one-track plan; its histograms (lufs on) and decision"""
+        L = capi.load()
+        s = MasteringJob._s(stream)
+        one, meas = self.one, self.meas
+        one.dd.lufs_on = 1 if lufs_on else 0
+        capi.check(L.amx_mc_split_pairs(capi.ptr(src), n, self.C, capi.ptr(meas.out), s), "amx_mc_split_pairs")
+        meas.loudness_pass1(stream, tail=False)
+        if lufs_on:
+            meas.loudness_pass2(stream, carry=False)
+        capi.check(L.amx_mc_loudness_combine(capi.ptr(meas.hops), int(meas.max_hops), capi.ptr(meas.peak),
+                                             self.C, capi.ptr(one.hops), capi.ptr(one.peak), s),
+                   "amx_mc_loudness_combine")
+        if lufs_on:
+            one.histograms(stream)
+        one.decide(stream)
+
+    def limit(self, src, dst, n, stream):
+        """the decided gain and the alimiter on src int16 [n, C] -> dst: the per-frame peak
+        signal through the one-track plan's limiter, its attenuation applied to every channel"""
+        L = capi.load()
+        s = MasteringJob._s(stream)
+        one = self.one
+        capi.check(L.amx_mc_peak_pick(capi.ptr(src), n, self.C, capi.ptr(one.gains), capi.ptr(one.out), s),
+                   "amx_mc_peak_pick")
+        one.finalize(None, stream)
+        capi.check(L.amx_mc_limiter_out(one.plan.h, one.fd, capi.ptr(src), self.C, capi.ptr(one.gains),
+                                        capi.ptr(one.ctl), capi.ptr(self.att), capi.ptr(dst), s),
+                   "amx_mc_limiter_out")
+
+    def close(self):
+        self.meas.close()
+        self.one.close()
+
+
 class MultiChannelJob:
     """One whole track with 3..8 channels (missing item 1).
 
@@ -652,21 +718,7 @@ class MultiChannelJob:
         self.ws = torch.empty(max(1, self.plan.workspace_bytes), dtype=torch.uint8, device=dev)
         self.out = torch.empty((max(1, n), C), dtype=torch.int16, device=dev)
         self.y = torch.empty_like(self.out)
-        P = (C + 1) // 2
-        lufs = self.settings.get("lufs")
-        m = max(1, n)
-        self.meas = MasteringJob(self.fs, 2, {"lufs": lufs}, [m] * P, input_s16=True,
-                                 chunks=[(p, p * m, m) for p in range(P)], device=dev, measure_only=True,
-                                 limiter=limiter)
-        self.one = MasteringJob(self.fs, 2, {"lufs": lufs}, [m], input_s16=True, chunks=[(0, 0, m)],
-                                device=dev, measure_only=True, limiter=limiter)
-        assert self.meas.max_hops == self.one.max_hops
-        self.att = torch.ones(m, dtype=torch.float64, device=dev)
-        capi.check(capi.load().amx_plan_set_limiter_trace(self.one.plan.h, capi.ptr(self.att)),
-                   "amx_plan_set_limiter_trace")
-        # af_alimiter's attack slope is / (C B) * C: the peak signal's stereo run takes C there
-        capi.check(capi.load().amx_plan_set_limiter_channels(self.one.plan.h, C),
-                   "amx_plan_set_limiter_channels")
+        self.stages = McStages(self.fs, C, n, self.settings.get("lufs"), limiter, 128, dev)
         self.report = {}
 
     _s = staticmethod(MasteringJob._s)
@@ -682,40 +734,20 @@ class MultiChannelJob:
         capi.check(capi.load().amx_mc_run_chunks(self.plan.h, capi.ptr(d_in), capi.ptr(self.out),
                                                  capi.ptr(self.ws), self._s(stream)), "amx_mc_run_chunks")
 
+    meas = property(lambda self: self.stages.meas)
+    one = property(lambda self: self.stages.one)
+    att = property(lambda self: self.stages.att)
+
     def measure(self, stream=None, lufs_on=None):
-        """loudnorm pass 1's measurement (:229) over the C channels: every channel's 192 kHz
-        K-weighted hop energies and peaks (the pairs as tracks), combined with the channel
-        weights into the one-track plan; its histograms (lufs on) and decision"""
-        L = capi.load()
-        s = self._s(stream)
-        n = self.out_frames
-        one, meas = self.one, self.meas
+        """loudnorm pass 1's measurement (:229) over the C channels (McStages.measure);
+        lufs_on None: as the settings say"""
         if lufs_on is None:
-            lufs_on = one.dd.lufs_on
-        one.dd.lufs_on = 1 if lufs_on else 0
-        capi.check(L.amx_mc_split_pairs(capi.ptr(self.out), n, self.C, capi.ptr(meas.out), s),
-                   "amx_mc_split_pairs")
-        meas.loudness_pass1(stream, tail=False)
-        if lufs_on:
-            meas.loudness_pass2(stream, carry=False)
-        capi.check(L.amx_mc_loudness_combine(capi.ptr(meas.hops), int(meas.max_hops), capi.ptr(meas.peak),
-                                             self.C, capi.ptr(one.hops), capi.ptr(one.peak), s),
-                   "amx_mc_loudness_combine")
-        if lufs_on:
-            one.histograms(stream)
-        one.decide(stream)
+            lufs_on = self.one.dd.lufs_on
+        self.stages.measure(self.out, self.out_frames, stream, lufs_on)
 
     def finalize(self, stream=None):
         """:240's linear gain and :223's alimiter on the C channels -> self.y"""
-        L = capi.load()
-        s = self._s(stream)
-        one = self.one
-        capi.check(L.amx_mc_peak_pick(capi.ptr(self.out), self.out_frames, self.C, capi.ptr(one.gains),
-                                      capi.ptr(one.out), s), "amx_mc_peak_pick")
-        one.finalize(None, stream)
-        capi.check(L.amx_mc_limiter_out(one.plan.h, one.fd, capi.ptr(self.out), self.C, capi.ptr(one.gains),
-                                        capi.ptr(one.ctl), capi.ptr(self.att), capi.ptr(self.y), s),
-                   "amx_mc_limiter_out")
+        self.stages.limit(self.out, self.y, self.out_frames, stream)
         return self.y[:self.out_frames]
 
     def fetch_report(self, raise_dynamic=True):
@@ -736,35 +768,24 @@ class MultiChannelJob:
     # --------------------------------------------- loudnorm dynamic mode (192 kHz)
     def _side192(self):
         """The 192 kHz side of the track, made once per job (creating a plan synchronises
-        the device): amx_mc_loudnorm_192k's scratch and output, a P-track and a one-track
-        measure plan at 192 kHz (the filter output's loudness gives pass 1's
-        target_offset) and the C-channel alimiter on the one-track plan (att trace,
-        amx_plan_set_limiter_channels), as __init__ sets them up at the input rate."""
-        side = getattr(self, "_s192", None)
-        if side is not None:
-            return side
+        the device): the stage set at 192 kHz (the filter output's loudness gives pass 1's
+        target_offset; its alimiter is :223 on the 192 kHz file) with
+        amx_mc_loudnorm_192k's scratch (ws), the filter's output (y192), the alimiter's
+        (out) and the kernel's summary (summ)."""
+        s = getattr(self, "_s192", None)
+        if s is not None:
+            return s
         import ctypes
-        from types import SimpleNamespace
-        L = capi.load()
         C, dev = self.C, self.device
         n192, wsb = ctypes.c_int64(), ctypes.c_int64()
-        capi.check(L.amx_mc_loudnorm_192k_size(self.meas.plan.h, C, ctypes.byref(n192), ctypes.byref(wsb)),
+        capi.check(capi.load().amx_mc_loudnorm_192k_size(self.meas.plan.h, C, ctypes.byref(n192), ctypes.byref(wsb)),
                    "amx_mc_loudnorm_192k_size")
-        n = max(1, n192.value)
-        P = (C + 1) // 2
-        lufs = self.settings.get("lufs")
-        s = SimpleNamespace(n192=n192.value)
-        s.meas = MasteringJob(192000, 2, {"lufs": lufs}, [n] * P, input_s16=True,
-                              chunks=[(p, p * n, n) for p in range(P)], device=dev, measure_only=True,
-                              seg_frames=1024)              # the K scan's window at 192 kHz
-        s.one = MasteringJob(192000, 2, {"lufs": lufs}, [n], input_s16=True, chunks=[(0, 0, n)], device=dev,
-                             measure_only=True, seg_frames=1024, limiter=self.limiter)
-        s.att = torch.ones(n, dtype=torch.float64, device=dev)
-        capi.check(L.amx_plan_set_limiter_trace(s.one.plan.h, capi.ptr(s.att)), "amx_plan_set_limiter_trace")
-        capi.check(L.amx_plan_set_limiter_channels(s.one.plan.h, C), "amx_plan_set_limiter_channels")
+        # seg_frames 1024: the K scan's window at 192 kHz
+        s = McStages(192000, C, n192.value, self.settings.get("lufs"), self.limiter, 1024, dev)
+        s.n192 = n192.value
         s.ws = torch.empty(max(1, wsb.value), dtype=torch.uint8, device=dev)
-        s.y192 = torch.empty((n, C), dtype=torch.int16, device=dev)     # the filter's output
-        s.out = torch.empty_like(s.y192)                                  # the alimiter's
+        s.y192 = torch.empty((max(1, s.n192), C), dtype=torch.int16, device=dev)
+        s.out = torch.empty_like(s.y192)
         s.summ = torch.zeros(16, dtype=torch.float64, device=dev)
         self._s192 = s
         return s
@@ -780,46 +801,25 @@ class MultiChannelJob:
             self._s(stream)), "amx_mc_loudnorm_192k")
 
     def dyn_measure(self, stream=None, lufs_on=True):
-        """the 192 kHz measurement of the filter's output over the C channels (split pairs,
-        the P-track plan's passes, combine, histograms, decision); lufs off: the peaks only"""
-        L = capi.load()
+        """the 192 kHz measurement of the filter's output over the C channels; lufs off: the
+        peaks only"""
         s = self._side192()
-        st = self._s(stream)
-        capi.check(L.amx_mc_split_pairs(capi.ptr(s.y192), s.n192, self.C, capi.ptr(s.meas.out), st),
-                   "amx_mc_split_pairs")
-        s.meas.loudness_pass1(stream, tail=False)
-        if lufs_on:
-            s.meas.loudness_pass2(stream, carry=False)
-        capi.check(L.amx_mc_loudness_combine(capi.ptr(s.meas.hops), int(s.meas.max_hops), capi.ptr(s.meas.peak),
-                                             self.C, capi.ptr(s.one.hops), capi.ptr(s.one.peak), st),
-                   "amx_mc_loudness_combine")
-        if lufs_on:
-            s.one.histograms(stream)
-        s.one.dd.lufs_on = 1 if lufs_on else 0
-        s.one.decide(stream)
+        s.measure(s.y192, s.n192, stream, lufs_on)
 
     def dyn_limit(self, stream=None):
         """:223 on the 192 kHz file: the C-channel alimiter over y192 -> the side's out.  Its
         input bound is af_loudnorm's ceiling (ln_output_bound); a track under 3 s (the
         unclamped linear fallback) measures it."""
-        L = capi.load()
         s = self._side192()
-        st = self._s(stream)
         bound = ln_output_bound(s.n192)
         if bound is not None:
-            with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+            with on_stream(stream):
                 s.one.peak.fill_(bound)
             s.one.dd.lufs_on = 0
             s.one.decide(stream)
         else:
-            self.dyn_measure(stream, lufs_on=False)
-        one = s.one
-        capi.check(L.amx_mc_peak_pick(capi.ptr(s.y192), s.n192, self.C, capi.ptr(one.gains), capi.ptr(one.out), st),
-                   "amx_mc_peak_pick")
-        one.finalize(None, stream)
-        capi.check(L.amx_mc_limiter_out(one.plan.h, one.fd, capi.ptr(s.y192), self.C, capi.ptr(one.gains),
-                                        capi.ptr(one.ctl), capi.ptr(s.att), capi.ptr(s.out), st),
-                   "amx_mc_limiter_out")
+            s.measure(s.y192, s.n192, stream, False)
+        s.limit(s.y192, s.out, s.n192, stream)
 
     def dynamic(self, stats, stream=None):
         """loudnorm's dynamic mode for the track (:240 when the linear conditions fail), the
@@ -829,14 +829,14 @@ class MultiChannelJob:
         strings `stats` (fetch_report's) and that offset, on pass 1's 192 kHz stream; the
         C-channel alimiter at 192 kHz.  Needs measure() with lufs on before it.  Returns
         (int16 [n192, C] at 192 kHz, info).  The filter is the frame-by-frame kernel
-        k_ln_dyn_mc; the host reads pass 1's loudness in between (this
+        k_ln_dyn<C>; the host reads pass 1's loudness in between (this
         path already synchronises in fetch_report)."""
         s = self._side192()
         target = float(self.settings["lufs"])
         d1 = capi.LoudnormDesc(target, LOUDNORM_LRA, LOUDNORM_TP, 0.0, 0.0, 99.0, -70.0, 0.0)
         self.dyn_filter(d1, stream)
         self.dyn_measure(stream, lufs_on=True)
-        with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+        with on_stream(stream):
             i_out = float(s.one.stats[0, 0].item())                 # pass 1's output loudness
         offset = loudness._fmt(target - i_out)
         d2 = capi.LoudnormDesc(target, LOUDNORM_LRA, LOUDNORM_TP, float(stats["input_i"]),
@@ -845,7 +845,7 @@ class MultiChannelJob:
         d2.reuse_stream = 1
         self.dyn_filter(d2, stream)
         self.dyn_limit(stream)
-        with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+        with on_stream(stream):
             prof = s.summ.cpu().numpy()
         info = {"target_offset": offset, "pass1_output_i": i_out, "sample_rate": 192000,
                 "linear_fallback": bool(prof[0] == 1.0)}
@@ -859,13 +859,10 @@ class MultiChannelJob:
             return
         self._closed = True
         torch.cuda.synchronize(self.device)
-        side = getattr(self, "_s192", None)
-        if side is not None:
-            side.meas.close()
-            side.one.close()
+        if getattr(self, "_s192", None) is not None:
+            self._s192.close()
             self._s192 = None
-        self.meas.close()
-        self.one.close()
+        self.stages.close()
         self.plan.close()
 
     def __enter__(self):

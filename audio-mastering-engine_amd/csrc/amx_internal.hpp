@@ -172,20 +172,27 @@ struct UpArgs {
     int64_t *part_hop;
     uint32_t *pk;                 // [seg][4]: 192 kHz |u| max L, R (float bits), native |x| L, R
 };
-// af_loudnorm's 192 kHz modes on one whole track (amx_loudnorm.hip)
+// af_loudnorm's 192 kHz modes on one whole track of C = 2..8 channels, frame by frame
+// (amx_ln_dyn.hip k_ln_dyn<C>)
 struct LnArgs {
     int64_t n192;                 // 192 kHz frames
-    float *u;                     // [n192][2] the resampled stream (scratch)
-    double *ring;                 // limiter ring [40320][2] + 64 (scratch)
-    int16_t *y;                   // [n192][2] output
-    double *summary;              // [2]: 1 = the < 3 s linear fallback ran (then [1] = its offset)
-    const double *hops;           // [>= n192 / 19200][2] pass-1 hop energies of this stream
-    const double *peak;           // [2] pass-1 192 kHz sample peak per channel
+    float *u;                     // [P][n192][2] the channel pairs' resampled streams, P = (C + 1) / 2:
+                                  // channel c is lane c & 1 of plane c >> 1 (scratch)
+    int64_t plane;                // floats from one plane to the next
+    double *ring;                 // limiter ring, AMX_LN_MC_RING(C) doubles (scratch)
+    int16_t *y;                   // [n192][C] output
+    double *summary;              // [16] 0: 1 = the < 3 s linear fallback ran (then [1] = its offset), else
+                                  // [1] = above_threshold at the end; 2..9 LnProf
+    const double *hops;           // [>= n192 / 19200 + 1][2] pass-1 hop energies of this stream (C >= 3:
+                                  // the combined ones, lane 1 is 0)
+    const double *peak;           // [2] pass-1 192 kHz sample peak per channel (C >= 3: the largest
+                                  // channel's in both lanes)
     const double *energies, *bounds;
     double target_i, target_lra, target_tp;   // target_tp linear (the ceiling)
     double measured_i, measured_thresh, offset;   // offset linear
     double weights[21];           // init_gaussian_filter
     double kb[5], ka[5];          // libebur128 K filter at 192 kHz (direct form)
+    // stereo only (NULL / unread for C >= 3)
     // set when the parallel form (LpArgs) runs first: this kernel then only runs the
     // tracks it hands over (lp_ctl[0] != 0) with the options it resolved (lp_dctl)
     int *lp_ctl;
@@ -201,6 +208,8 @@ struct LnArgs {
     // the replicated form (lp_ctl[0] stays 1).  INT_MAX otherwise.
     int lp_tstop;
 };
+#define AMX_LN_MC_RING(C) ((int64_t)(C) * AMX_LN_RING + 64)   // doubles: the ring and its slack (>= C)
+hipError_t launch_ln_dyn(const LnArgs &a, int C, int phase, hipStream_t st);
 // af_loudnorm dynamic mode in parallel form (amx_loudnorm.hip):
 // per-frame statistics and gains from pass 1's hop energies, then the true-peak
 // limiter as warmed-up segments of 100 ms frames with an in-order check and repair.
@@ -271,26 +280,6 @@ hipError_t launch_loudnorm_shard(const LnArgs &a, const LpArgs &p, const uint32_
 // the upsample step alone: [j0, j1) of the 192 kHz stream of one stereo s16 plane into u
 hipError_t launch_ln_upsample(const uint32_t *x, int64_t n_in, const SwrDev &r, int64_t j0, int64_t j1, float *u,
                               const int32_t *gate, hipStream_t st);
-// af_loudnorm's 192 kHz modes on one whole track of C = 3..8 channels, frame by frame
-// (amx_mc_loudnorm.hip k_ln_dyn_mc<C>)
-struct LnMcArgs {
-    int64_t n192;                 // 192 kHz frames
-    const float *u;               // [P][n192][2] the channel pairs' resampled streams, P = (C + 1) / 2:
-                                  // channel c is lane c & 1 of plane c >> 1
-    int64_t plane;                // floats from one plane to the next
-    double *ring;                 // limiter ring [40320][C] + C doubles of slack (scratch)
-    int16_t *y;                   // [n192][C] output
-    double *summary;              // [16] as LnArgs::summary
-    const double *hops;           // [>= n192 / 19200 + 1][2] the combined hop energies (lane 1: 0)
-    const double *peak;           // [2] the largest channel's 192 kHz sample peak (both lanes)
-    const double *energies, *bounds;
-    double target_i, target_lra, target_tp;       // target_tp linear (the ceiling)
-    double measured_i, measured_thresh, offset;   // offset linear
-    double weights[21];           // init_gaussian_filter
-    double kb[5], ka[5];          // libebur128 K filter at 192 kHz (direct form)
-};
-#define AMX_LN_MC_RING(C) ((int64_t)(C) * AMX_LN_RING + 64)   // doubles: the ring and its slack (>= C)
-hipError_t launch_mc_loudnorm(const LnMcArgs &a, int C, hipStream_t st);
 #define AMX_LN_GATED(g) ((g) && (((g)[0] >> 4) & 15) != 3)   // k_decide mode 3 = dynamic
 hipError_t launch_up1(const UpArgs &a, hipStream_t st, hipStream_t aux, hipEvent_t fork, hipEvent_t join);
 hipError_t launch_up2(const UpArgs &a, hipStream_t st);

@@ -1,5 +1,5 @@
-// amx_ln_dev.hpp -- what af_loudnorm's frame-by-frame kernels share: k_ln_dyn
-// (amx_loudnorm.hip, stereo) and k_ln_dyn_mc<C> (amx_mc_loudnorm.hip, 3..8 channels).
+// amx_ln_dev.hpp -- what af_loudnorm's frame-by-frame kernel k_ln_dyn<C> (amx_ln_dyn.hip,
+// 2..8 channels) shares with the parallel form's k_lp_* (amx_loudnorm.hip, stereo).
 // The frame geometry at 192 kHz, the workgroup reductions, the s16 conversion and
 // r128_in's statistics from pass 1's hop energies (gating-block histogram, gated
 // integrated loudness, relative gate, 3 s short-term).  The statistics read one track's
@@ -73,7 +73,7 @@ __device__ __forceinline__ int16_t ln_s16_lim(double v) {
     return (int16_t)(int)fmin(fmax(rint(v * 32768.0), -32768.0), 32767.0);
 }
 
-// the workgroup's LDS, CH the channel count of the scan rows (k_ln_dyn: 2)
+// k_ln_dyn's LDS, CH the channel count of the scan rows
 template <int CH>
 struct LnSharedT {
     unsigned hist[1000];               // r128_in's gating-block histogram, rebuilt here
@@ -85,7 +85,6 @@ struct LnSharedT {
     double sbuf[1001];                 // ln_seq_sum
     int scan[LN_NW + 1];
 };
-using LnShared = LnSharedT<2>;
 
 __device__ __forceinline__ int ln_find_bin(const double *B, double e) {
     int lo = 0, hi = 1000;

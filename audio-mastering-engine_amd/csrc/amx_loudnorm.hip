@@ -7,33 +7,18 @@
 //   k_ln_upsample: the 192 kHz stream libswresample feeds the filter (the same float32
 //     polyphase FIR, window and FMA3 summation order as amx_loud192.hip), stored once as
 //     float32 [frames][2] -- the filter reads it up to 3 s behind its output.
-//   k_ln_dyn: the filter itself, one workgroup per track.  af_loudnorm is a state machine
-//     over 100 ms frames (the AGC gain of a frame depends on the previous frames'
-//     decisions) whose true-peak limiter is a state machine over samples, so it runs in
-//     order; the workgroup shares out the per-sample loops:
-//       - the limiter ring fills (gain ramp x offset) and the output (clamp, s16);
-//       - detect_peak: a block-wide minimum finds the first position that can be a peak
-//         (prev <= |x| >= next, |x| > ceiling); only from there on is the scan serial
-//         (a candidate that fails the 10-sample look-ahead keeps the previous sample,
-//         so later positions depend on it);
-//       - the envelope loops of ATTACK / SUSTAIN / RELEASE (each thread one sample);
-//     and the scalar parts (Gaussian smoothing, statistics, delta, limiter state) are
-//     carried by every thread alike.  The input-side loudness statistics af_loudnorm reads from r128_in
-//     after each frame (3 s short-term, gated integrated, relative gate) come from the
-//     hop energies loudness pass 1 measured on this same 192 kHz stream; the
-//     histogram is rebuilt in LDS block by block.  r128_out (the output's short-term
-//     loudness) is only read while above_threshold is 0; libebur128's K filter then runs
-//     over the frame's output on two threads (one per channel).
+//   k_lp_*: the filter in parallel form (below).  The frame-by-frame form, k_ln_dyn<C>,
+//     is amx_ln_dyn.hip; launch_loudnorm runs it (C = 2) before and after the parallel
+//     form for the tracks that one does not take.
 // Floating point: no FMA contraction (the reference's C is compiled that way too,
 // -ffp-contract=off in the oracle), so every expression keeps its operation order.
 #include "amx_dev.hpp"
-#include "amx_ln_dev.hpp"    // the frame geometry, block helpers and r128_in statistics (shared with k_ln_dyn_mc)
+#include "amx_ln_dev.hpp"    // the frame geometry, block helpers and r128_in statistics (shared with k_ln_dyn)
 
 #pragma clang fp contract(off)
 
 namespace amx {
 
-#define LN_RSZ (2 * LN_LIMF) // limiter ring samples
 #define LN_TAPS 32
 #define LN_C 15
 
@@ -277,566 +262,8 @@ __global__ void __launch_bounds__(AMX_BLOCK) k_ln_upsample_wide(const uint32_t *
     }
 }
 
-__device__ __forceinline__ int ln_w(int i) { return i < LN_RSZ ? i : i - LN_RSZ; }
-__device__ __forceinline__ int ln_wrap(int i) {
-    while (i >= LN_RSZ) i -= LN_RSZ;
-    return i;
-}
-
-// ------------------------------------------------------------ the filter
-struct LnLim {                   // true_peak_limiter state (block-uniform)
-    int state, env_cnt, env_index, peak_index, attack_length;
-    double gr0, gr1, prev[2];
-};
-
-// detect_peak from output offset `offset` over `count` positions: returns peak_delta
-// (-1: none) and sets peak_value, peak_index, prev[].  Groups of LN_NT positions: each
-// thread stages one position's |x| (and threads < 12 the positions after the group:
-// the next sample and the 10-sample look-ahead read past a position; the ring always
-// holds real samples there); the first position that is a candidate with the normal
-// predecessor (the previous sample) is found by a block-wide minimum, and only from
-// there on is the scan serial (a candidate that fails the look-ahead keeps the older
-// predecessor, so later positions depend on it), every thread stepping it alike.
-__device__ int ln_detect(const double *ring, LnLim &S, int lbi, int offset, int count, bool first,
-                         double ceiling, double &peak_value, LnShared &L, LnProf &P) {
-    P.n_detect++;
-    const int tid = threadIdx.x;
-    int index = lbi + (offset * 2) + (LN_ATT * 2);
-    if (index >= LN_RSZ) index -= LN_RSZ;
-    if (first) {
-        S.prev[0] = fabs(ring[index - 2]);
-        S.prev[1] = fabs(ring[index - 1]);
-    }
-    for (int base = 0; base < count; base += LN_NT) {
-        {
-            const int idx = ln_wrap(index + 2 * (base + tid));
-            const double a0 = fabs(ring[idx]), a1 = fabs(ring[idx + 1]);
-            double b0 = 0.0, b1 = 0.0;
-            if (tid < 12) {
-                const int jx = ln_wrap(index + 2 * (base + LN_NT + tid));
-                b0 = fabs(ring[jx]);
-                b1 = fabs(ring[jx + 1]);
-            }
-            __syncthreads();                          // the previous group's reads are done
-            L.th[0][tid] = a0;
-            L.th[1][tid] = a1;
-            if (tid < 12) {
-                L.th[0][LN_NT + tid] = b0;
-                L.th[1][LN_NT + tid] = b1;
-            }
-            __syncthreads();
-        }
-        const int n = base + tid;
-        const int last = (count - base < LN_NT ? count - base : LN_NT) - 1;
-        bool cand = false;
-        if (n < count) {
-#pragma unroll
-            for (int c = 0; c < 2; c++) {
-                const double th = L.th[c][tid], nx = L.th[c][tid + 1];
-                const double pv = tid == 0 ? S.prev[c] : L.th[c][tid - 1];
-                cand |= pv <= th && nx <= th && th > ceiling && n > 0;
-            }
-        }
-        const unsigned long long m = __ballot(cand);
-        if ((tid & 63) == 0) L.first[tid >> 6] = m ? (tid + __ffsll((long long)m) - 1) : LN_NT;
-        __syncthreads();
-        int L0 = LN_NT;
-#pragma unroll
-        for (int w = 0; w < LN_NW; w++) L0 = L.first[w] < L0 ? L.first[w] : L0;
-        if (L0 == LN_NT) {
-            S.prev[0] = L.th[0][last];
-            S.prev[1] = L.th[1][last];
-            continue;
-        }
-        P.n_serial++;
-        if (L0 > 0) {
-            S.prev[0] = L.th[0][L0 - 1];
-            S.prev[1] = L.th[1][L0 - 1];
-        }
-        for (int k = L0; k <= last; k++) {
-            const int nn = base + k;
-            for (int c = 0; c < 2; c++) {
-                const double t = L.th[c][k], nxt = L.th[c][k + 1];
-                if ((S.prev[c] <= t) && (nxt <= t) && (t > ceiling) && (nn > 0)) {
-                    bool detected = true;
-                    for (int i = 2; i < 12; i++)
-                        if (L.th[c][k + i] > t) { detected = false; break; }
-                    if (!detected) continue;
-                    const double p0 = L.th[0][k], p1 = L.th[1][k];
-                    double mp = p0;
-                    if (p1 > mp) mp = p1;
-                    S.prev[0] = p0;
-                    S.prev[1] = p1;
-                    S.peak_index = ln_wrap(index + 2 * nn);
-                    peak_value = mp;
-                    return nn;
-                }
-                S.prev[c] = t;
-            }
-        }
-    }
-    return -1;
-}
-
-// apply env(i) to the k ring frames from env_index on (env_index may be the ring size
-// itself, as in af_loudnorm: that first write falls outside the ring)
-template <class F>
-__device__ __forceinline__ void ln_env_apply(double *ring, int e0, int k, F env) {
-    const int tid = threadIdx.x;
-    constexpr int U = 4;
-    for (int i0 = 0; i0 < k; i0 += LN_NT * U) {
-        int sl[U];
-        double r0[U], r1[U];
-#pragma unroll
-        for (int q = 0; q < U; q++) {
-            const int i = i0 + LN_NT * q + tid;
-            sl[q] = i > 0 ? ln_wrap(e0 + 2 * i) : e0;
-            r0[q] = i < k ? ring[sl[q]] : 0.0;
-            r1[q] = i < k ? ring[sl[q] + 1] : 0.0;
-        }
-#pragma unroll
-        for (int q = 0; q < U; q++) {
-            const int i = i0 + LN_NT * q + tid;
-            if (i < k) {
-                const double g = env(i);
-                ring[sl[q]] = r0[q] * g;
-                ring[sl[q] + 1] = r1[q] * g;
-            }
-        }
-    }
-    __syncthreads();
-}
-
-__device__ __forceinline__ int ln_env_end(int e0, int k) {
-    if (k <= 0) return e0;
-    int e = e0 + 2 * (k - 1);
-    if (k > 1) e = ln_wrap(e);
-    e += 2;
-    if (e >= LN_RSZ) e -= LN_RSZ;
-    return e;
-}
-
-// true_peak_limiter: nb output frames from ring position lbi into y (s16)
-__device__ void ln_limiter(double *ring, LnLim &S, int lbi, int nb, bool first, double ceiling,
-                           int16_t *y, LnShared &L, LnProf &P) {
-    const int tid = threadIdx.x;
-    if (first) {
-        double mx = 0.0;
-        for (int i = tid; i < LN_ATT; i += LN_NT) mx = fmax(mx, fmax(fabs(ring[2 * i]), fabs(ring[2 * i + 1])));
-        mx = ln_bmax(mx, L.red);
-        if (mx > ceiling) {
-            S.gr1 = ceiling / mx;
-            S.state = LIM_SUSTAIN_;
-            for (int i = tid; i < LN_ATT; i += LN_NT) {
-                ring[2 * i] *= S.gr1;
-                ring[2 * i + 1] *= S.gr1;
-            }
-            __syncthreads();
-        }
-    }
-    int smp = 0;
-    double pv = 0.0;
-    do {
-        switch (S.state) {
-        case LIM_OUT_: {
-            const uint64_t t0 = clock64();
-            const int pd = ln_detect(ring, S, lbi, smp, nb - smp, first, ceiling, pv, L, P);
-            P.detect += clock64() - t0;
-            if (pd != -1) {
-                S.env_cnt = 0;
-                smp += (pd - S.attack_length);
-                S.gr0 = 1.;
-                S.gr1 = ceiling / pv;
-                S.state = LIM_ATTACK_;
-                S.env_index = S.peak_index - (S.attack_length * 2);
-                if (S.env_index < 0) S.env_index += LN_RSZ;
-                S.env_index += (S.env_cnt * 2);
-                if (S.env_index > LN_RSZ) S.env_index -= LN_RSZ;
-            } else {
-                smp = nb;
-            }
-            break;
-        }
-        case LIM_ATTACK_: {
-            int k = S.attack_length - S.env_cnt;
-            if (k > nb - smp) k = nb - smp;
-            if (k < 0) k = 0;
-            const int c0 = S.env_cnt, al = S.attack_length;
-            const double g0 = S.gr0, g1 = S.gr1;
-            const uint64_t t0 = clock64();
-            ln_env_apply(ring, S.env_index, k,
-                         [&](int i) { return g0 - ((double)(c0 + i) / (al - 1) * (g0 - g1)); });
-            P.env += clock64() - t0;
-            S.env_index = ln_env_end(S.env_index, k);
-            S.env_cnt += k;
-            smp += k;
-            if (smp < nb) {
-                S.env_cnt = 0;
-                S.attack_length = LN_ATT;
-                S.state = LIM_SUSTAIN_;
-            }
-            break;
-        }
-        case LIM_SUSTAIN_: {
-            const uint64_t t0 = clock64();
-            const int pd = ln_detect(ring, S, lbi, smp, nb, first, ceiling, pv, L, P);
-            P.detect += clock64() - t0;
-            if (pd == -1) {
-                S.state = LIM_RELEASE_;
-                S.gr0 = S.gr1;
-                S.gr1 = 1.;
-                S.env_cnt = 0;
-                break;
-            }
-            const double gain_reduction = ceiling / pv;
-            if (gain_reduction < S.gr1) {
-                S.state = LIM_ATTACK_;
-                S.attack_length = pd;
-                if (S.attack_length <= 1) S.attack_length = 2;
-                S.gr0 = S.gr1;
-                S.gr1 = gain_reduction;
-                S.env_cnt = 0;
-                break;
-            }
-            int k = pd;
-            if (k > nb - smp) k = nb - smp;
-            if (k < 0) k = 0;
-            const double g1 = S.gr1;
-            const uint64_t t1 = clock64();
-            ln_env_apply(ring, S.env_index, k, [&](int) { return g1; });
-            P.env += clock64() - t1;
-            S.env_index = ln_env_end(S.env_index, k);
-            S.env_cnt = k;
-            smp += k;
-            break;
-        }
-        default: {   // RELEASE
-            const int rl = LN_FR;
-            int k = rl - S.env_cnt;
-            if (k > nb - smp) k = nb - smp;
-            if (k < 0) k = 0;
-            const int c0 = S.env_cnt;
-            const double g0 = S.gr0, g1 = S.gr1;
-            const uint64_t t0 = clock64();
-            ln_env_apply(ring, S.env_index, k,
-                         [&](int i) { return g0 + (((double)(c0 + i) / (rl - 1)) * (g1 - g0)); });
-            P.env += clock64() - t0;
-            S.env_index = ln_env_end(S.env_index, k);
-            S.env_cnt += k;
-            smp += k;
-            if (smp < nb) {
-                S.env_cnt = 0;
-                S.state = LIM_OUT_;
-            }
-            break;
-        }
-        }
-    } while (smp < nb);
-    const uint64_t t_out = clock64();
-    constexpr int U = 4;
-    for (int i0 = 0; i0 < nb; i0 += LN_NT * U) {
-        double r0[U], r1[U];
-#pragma unroll
-        for (int q = 0; q < U; q++) {
-            const int i = i0 + LN_NT * q + tid;
-            const int slot = ln_wrap(lbi + 2 * i);
-            r0[q] = i < nb ? ring[slot] : 0.0;
-            r1[q] = i < nb ? ring[slot + 1] : 0.0;
-        }
-#pragma unroll
-        for (int q = 0; q < U; q++) {
-            const int i = i0 + LN_NT * q + tid;
-            double o0 = r0[q], o1 = r1[q];
-            if (fabs(o0) > ceiling) o0 = ceiling * (o0 < 0 ? -1 : 1);
-            if (fabs(o1) > ceiling) o1 = ceiling * (o1 < 0 ? -1 : 1);
-            if (i < nb) {
-                y[2 * i] = ln_s16(o0);
-                y[2 * i + 1] = ln_s16(o1);
-            }
-        }
-    }
-    P.out += clock64() - t_out;
-}
-
-// libebur128's K filter (direct form) over the frame's clamped output, threads 0 / 1 one
-// channel each (r128_out, read only while above_threshold is 0): the frame's energy,
-// both channels, to every thread; DBL_MIN flush at the end as ebur128_filter does per call
-__device__ double ln_out_energy(const double *ring, int lbi, int nb, double ceiling, const double *kb,
-                                const double *ka, double (&kv)[5], double *s_red) {
-    const int tid = threadIdx.x;
-    double e = 0.0;
-    if (tid < 2) {
-        double *v = kv;
-        for (int i = 0; i < nb; i++) {
-            const int slot = ln_wrap(lbi + 2 * i);
-            double o = ring[slot + tid];
-            if (fabs(o) > ceiling) o = ceiling * (o < 0 ? -1 : 1);
-            v[0] = o - ka[1] * v[1] - ka[2] * v[2] - ka[3] * v[3] - ka[4] * v[4];
-            const double yv = kb[0] * v[0] + kb[1] * v[1] + kb[2] * v[2] + kb[3] * v[3] + kb[4] * v[4];
-            e += yv * yv;
-            v[4] = v[3]; v[3] = v[2]; v[2] = v[1]; v[1] = v[0];
-        }
-        for (int k = 1; k < 5; k++) v[k] = fabs(v[k]) < 2.2250738585072014e-308 ? 0.0 : v[k];
-    }
-    __syncthreads();
-    if (tid < 2) s_red[tid] = e;
-    __syncthreads();
-    const double r = s_red[0] + s_red[1];
-    __syncthreads();
-    return r;
-}
-
-// phase 0 (after k_lp_stats): the tracks the parallel form does not start -- the < 3 s
-// linear fallback, a quiet start (handed over at the first segment start after
-// above_threshold turns 1, lp_ctl[0] = 4); phase 1 (after k_lp_walk): a whole track the
-// walker handed back (lp_ctl[0] = 2), frame by frame to the end
-__global__ void __launch_bounds__(LN_NT) k_ln_dyn(LnArgs a0, int phase) {
-    if (a0.lp_ctl && a0.lp_ctl[0] != (phase == 0 ? 1 : 2)) return;
-    LnArgs a = a0;
-    if (a0.lp_dctl) {
-        a.offset = a0.lp_dctl[1];
-        a.measured_i = a0.lp_dctl[2];
-        a.measured_thresh = a0.lp_dctl[3];
-    }
-    __shared__ LnShared L;
-    const int tid = threadIdx.x;
-    for (int i = tid; i < 1000; i += LN_NT) { L.hist[i] = 0u; L.E[i] = a.energies[i]; }
-    for (int i = tid; i < 1001; i += LN_NT) L.B[i] = a.bounds[i];
-    if (tid < 30) L.oe[tid] = 0.0;
-    __syncthreads();
-    const int64_t n = a.n192;
-    const float *u = a.u;
-    double *ring = a.ring;
-    const double ceiling = a.target_tp;
-    LnProf P;
-    if (n < LN_FIRST) {
-        // the first frame is the whole input: af_loudnorm falls back to LINEAR_MODE with
-        // an offset from r128_in's integrated loudness and sample peak
-        for (int64_t k = 4; k * LN_FR <= n; k++) ln_add_block(L, a.hops, k);
-        double global, rel;
-        ln_global(L, global, rel);
-        const double true_peak = a.peak[0] > a.peak[1] ? a.peak[0] : a.peak[1];
-        const double offset = pow(10., (a.target_i - global) / 20.);
-        const double offset_tp = true_peak * offset;
-        const double off = offset_tp < a.target_tp ? offset : a.target_tp / true_peak;
-        for (int64_t j = tid; j < n; j += LN_NT) {
-            a.y[2 * j] = ln_s16((double)u[2 * j] * off);
-            a.y[2 * j + 1] = ln_s16((double)u[2 * j + 1] * off);
-        }
-        if (tid == 0) {
-            a.summary[0] = 1.0;
-            a.summary[1] = off;
-            for (int q = 10; q < 13; q++) a.summary[q] = 0.0;
-            a.summary[13] = (a0.lp_ctl && a0.lp_ctl[0] == 2) ? 1.0 : 0.0;
-        }
-        return;
-    }
-    // ---- FIRST frame (3 s)
-    for (int64_t k = 4; k <= LN_FIRST / LN_FR; k++) ln_add_block(L, a.hops, k);
-    double delta[30];
-    int index = 1, above;
-    double prev_delta;
-    {
-        const double shortterm = ln_shortterm(a.hops, LN_FIRST / LN_FR, L.red);
-        double env_shortterm;
-        if (shortterm < a.measured_thresh) {
-            above = 0;
-            env_shortterm = shortterm <= -70. ? 0. : a.target_i - a.measured_i;
-        } else {
-            above = 1;
-            env_shortterm = shortterm <= -70. ? 0. : a.target_i - shortterm;
-        }
-        const double d = pow(10., env_shortterm / 20.);
-#pragma unroll
-        for (int q = 0; q < 30; q++) delta[q] = d;
-        prev_delta = delta[index];
-    }
-    for (int i = tid; i < LN_LIMF; i += LN_NT) {
-        ring[2 * i] = (double)u[2 * i] * delta[1] * a.offset;
-        ring[2 * i + 1] = (double)u[2 * i + 1] * delta[1] * a.offset;
-    }
-    __syncthreads();
-    LnLim S{LIM_OUT_, 0, 0, 0, LN_ATT, 0.0, 0.0, {0.0, 0.0}};
-    int lbi = 0;
-    double kv[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-    int oe_i = 0;
-    auto out_feed = [&](int nb) {                        // r128_out, only while needed
-        const uint64_t t0 = clock64();
-        const double e = ln_out_energy(ring, lbi, nb, ceiling, a.kb, a.ka, kv, L.red);
-        if (tid == 0) L.oe[oe_i] = e;
-        oe_i = oe_i + 1 < 30 ? oe_i + 1 : 0;
-        __syncthreads();
-        P.feed += clock64() - t0;
-    };
-    int64_t out_pos = 0;
-    ln_limiter(ring, S, lbi, LN_FR, true, ceiling, a.y, L, P);
-    if (above == 0) out_feed(LN_FR);
-    out_pos = LN_FR;
-    int64_t R = LN_LIMF, Pin = LN_FIRST;
-    auto gauss = [&](int idx) {
-        double r = 0.;
-        idx = idx - 10 > 0 ? idx - 10 : idx + 20;
-#pragma unroll
-        for (int i = 0; i < 21; i++) r += delta[((idx + i) < 30) ? (idx + i) : (idx + i - 30)] * a.weights[i];
-        return r;
-    };
-    int ho_f = -1, ho_k = -1;                            // hand-over frame / segment (quiet start)
-    // ---- INNER frames (100 ms)
-    while (Pin < n) {
-        const int t_in = (int)((Pin - LN_FIRST) / LN_FR);     // this INNER frame
-        if (phase == 0 && t_in >= a0.lp_tstop) return;        // (a shard: past rank 0's frames)
-        const int nb = (int)(n - Pin < LN_FR ? n - Pin : LN_FR);
-        const uint64_t t_fill = clock64();
-        const double gain = gauss(index + 10 < 30 ? index + 10 : index + 10 - 30);
-        const double gain_next = gauss(index + 11 < 30 ? index + 11 : index + 11 - 30);
-        {
-            constexpr int U = 4;
-            for (int i0 = 0; i0 < nb; i0 += LN_NT * U) {
-                float v0[U], v1[U];
-#pragma unroll
-                for (int q = 0; q < U; q++) {
-                    const int i = i0 + LN_NT * q + tid;
-                    v0[q] = i < nb ? u[2 * (R + i)] : 0.0f;
-                    v1[q] = i < nb ? u[2 * (R + i) + 1] : 0.0f;
-                }
-#pragma unroll
-                for (int q = 0; q < U; q++) {
-                    const int i = i0 + LN_NT * q + tid;
-                    if (i < nb) {
-                        const int slot = ln_wrap(lbi + 2 * i);
-                        const double g = gain + (((double)i / nb) * (gain_next - gain));
-                        ring[slot] = (double)v0[q] * g * a.offset;
-                        ring[slot + 1] = (double)v1[q] * g * a.offset;
-                    }
-                }
-            }
-        }
-        __syncthreads();
-        lbi = ln_wrap(lbi + 2 * nb);
-        {
-            const int sub = (LN_FR - nb) * 2;
-            lbi = lbi + sub < LN_RSZ ? lbi + sub : lbi + sub - LN_RSZ;
-        }
-        R += nb;
-        Pin += nb;
-        P.fill += clock64() - t_fill;
-        ln_limiter(ring, S, lbi, nb, false, ceiling, a.y + 2 * out_pos, L, P);
-        if (above == 0) out_feed(nb);
-        const uint64_t t_stats = clock64();
-        out_pos += nb;
-        // r128_in after this frame: a full frame ends on hop Pin / 19200 (one new block)
-        const int64_t hk = Pin / LN_FR;
-        if (nb == LN_FR) ln_add_block(L, a.hops, hk);
-        double global, relative_threshold;
-        ln_global(L, global, relative_threshold);
-        const double shortterm = ln_shortterm(a.hops, hk, L.red);
-        if (above == 0) {
-            if (shortterm > a.measured_thresh) prev_delta *= 1.0058;
-            double so = 0.0;
-            for (int q = 0; q < 30; q++) so += L.oe[q];
-            const double shortterm_out = 10 * log10(so / (double)LN_FIRST) - 0.691;
-            if (shortterm_out >= a.target_i) above = 1;
-        }
-        double dnew;
-        if (shortterm < relative_threshold || shortterm <= -70. || above == 0) {
-            dnew = prev_delta;
-        } else {
-            const double env_global = fabs(shortterm - global) < (a.target_lra / 2.)
-                                          ? shortterm - global
-                                          : (a.target_lra / 2.) * ((shortterm - global) < 0 ? -1 : 1);
-            const double env_shortterm = a.target_i - shortterm;
-            dnew = pow(10., (env_global + env_shortterm) / 20.);
-        }
-#pragma unroll
-        for (int q = 0; q < 30; q++) delta[q] = q == index ? dnew : delta[q];
-        prev_delta = dnew;
-        index = index + 1 < 30 ? index + 1 : 0;
-        P.stats += clock64() - t_stats;
-        if (a0.lp_D && tid == 0) a0.lp_D[t_in] = dnew;
-        if (phase == 0 && a0.lp_recG && above && ho_f < 0) {
-            // from here the deltas follow r128_in alone: hand over at the next segment
-            // start (frame 1 + k Fs, k <= J) -- after frame ho_f - 1, before ho_f's fill
-            const int phi = t_in + 1;
-            int k = (phi + a0.lp_Fs - 1) / a0.lp_Fs;
-            if (k < 1) k = 1;
-            if (k <= a0.lp_J) {
-                ho_k = k;
-                ho_f = 1 + k * a0.lp_Fs;
-            } else {
-                ho_f = 0;                                      // none left: run to the end
-            }
-        }
-        if (ho_f > 0 && t_in + 1 == ho_f - 1) {
-            // the state at frame ho_f's start, as k_lp_snapshot records it: the limiter
-            // scalars (envelope slot in frames) and the 2048 ring slots from the frame's
-            // first output position (19200 ho_f; INNER slot = position mod the ring)
-            double *rec = a0.lp_recG + (int64_t)ho_k * AMX_LN_REC;
-            if (tid == 0) {
-                rec[0] = S.state;
-                rec[1] = S.env_cnt;
-                rec[2] = S.env_index / 2;
-                rec[3] = S.attack_length;
-                rec[4] = S.gr0;
-                rec[5] = S.gr1;
-                rec[6] = ho_f;
-                rec[7] = 0.0;
-                a0.lp_ctl[0] = 4;
-                a0.lp_ctl[4] = ho_k;
-                a0.lp_ctl[5] = ho_f;
-            }
-            const int s0 = (int)(((int64_t)LN_FR * ho_f) % LN_LIMF);
-            for (int j = tid; j < AMX_LN_WIN; j += LN_NT) {
-                const int sl = s0 + j < LN_LIMF ? s0 + j : s0 + j - LN_LIMF;
-                rec[16 + 2 * j] = ring[2 * sl];
-                rec[17 + 2 * j] = ring[2 * sl + 1];
-            }
-            return;
-        }
-    }
-    // ---- FINAL frame (flush_frame: the last 3 s less one frame, re-read)
-    {
-        const int nbf = LN_FIRST - LN_FR;                // (buf_size - prev_nb) - (100 ms - prev_nb)
-        const int64_t S0 = n - nbf;                      // its first frame in the stream
-        const double gain = gauss(index + 10 < 30 ? index + 10 : index + 10 - 30);
-        for (int i = tid; i < LN_LIMF; i += LN_NT) {
-            ring[2 * i] = (double)u[2 * (S0 + i)] * gain * a.offset;
-            ring[2 * i + 1] = (double)u[2 * (S0 + i) + 1] * gain * a.offset;
-        }
-        __syncthreads();
-        lbi = 0;
-        int64_t src = LN_LIMF;
-        for (int it = 0; it < nbf / LN_FR; it++) {
-            ln_limiter(ring, S, lbi, LN_FR, false, ceiling, a.y + 2 * out_pos, L, P);
-            for (int i = tid; i < LN_FR; i += LN_NT) {
-                const int slot = ln_wrap(lbi + 2 * i);
-                const bool in = src + i < nbf;
-                ring[slot] = in ? (double)u[2 * (S0 + src + i)] * gain * a.offset : 0.;
-                ring[slot + 1] = in ? (double)u[2 * (S0 + src + i) + 1] * gain * a.offset : 0.;
-            }
-            __syncthreads();
-            src += LN_FR;
-            lbi = ln_wrap(lbi + 2 * LN_FR);
-            out_pos += LN_FR;
-        }
-    }
-    if (tid == 0) {
-        a.summary[0] = 0.0;
-        a.summary[1] = (double)above;
-        a.summary[2] = (double)P.fill;
-        a.summary[3] = (double)P.detect;
-        a.summary[4] = (double)P.env;
-        a.summary[5] = (double)P.out;
-        a.summary[6] = (double)P.stats;
-        a.summary[7] = (double)P.feed;
-        a.summary[8] = (double)P.n_detect;
-        a.summary[9] = (double)P.n_serial;
-        for (int q = 10; q < 13; q++) a.summary[q] = 0.0;
-        a.summary[13] = (a0.lp_ctl && a0.lp_ctl[0] == 2) ? 1.0 : 0.0;   // handed over by k_lp_walk
-    }
-}
-
 // ======================================================================
-// Dynamic mode in parallel form.  k_ln_dyn above runs af_loudnorm
+// Dynamic mode in parallel form.  k_ln_dyn (amx_ln_dyn.hip) runs af_loudnorm
 // frame by frame on one workgroup; it stays the path for the < 3 s linear fallback
 // and for a track whose first 3 s are below measured_thresh (above_threshold 0: the
 // output's own short-term loudness then steers the gains).  Every other track -- the
@@ -2119,7 +1546,7 @@ static void ln_upsample(const uint32_t *x, int64_t n_in, const SwrDev &r, int64_
 }
 
 // the upsample step on its own: launch_loudnorm's for a stereo track, and one call per
-// channel pair of a C-channel track (amx_mc_loudnorm.hip)
+// channel pair of a C-channel track (amx_mc_loudnorm_192k)
 hipError_t launch_ln_upsample(const uint32_t *x, int64_t n_in, const SwrDev &r, int64_t j0, int64_t j1, float *u,
                               const int32_t *gate, hipStream_t st) {
     ln_upsample(x, n_in, r, j0, j1, u, gate, st);
@@ -2134,11 +1561,12 @@ hipError_t launch_loudnorm(const LnArgs &ln, const LpArgs &lp, const uint32_t *x
     // energies alone and stand -- only block 0, the resolved options, runs
     hipLaunchKernelGGL(k_lp_stats, dim3(resample ? 1 + (lp.T + LP_STAT_F - 1) / LP_STAT_F : 1), dim3(LP_STAT_NT), 0,
                        st, lp);
-    hipLaunchKernelGGL(k_ln_dyn, dim3(1), dim3(LN_NT), 0, st, ln, 0);
+    hipError_t e = launch_ln_dyn(ln, 2, 0, st);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_lp_dscan, dim3(1), dim3(1024), 0, st, lp);
     const int gb = max((lp.T + 1 + 255) / 256, (LP_FR + 255) / 256);
     hipLaunchKernelGGL(k_lp_gains, dim3(gb), dim3(256), 0, st, lp);
-    hipError_t e = lp.bm ? lp_fill(lp, 0, ln.n192, 0, ln.n192, st) : hipSuccess;
+    e = lp.bm ? lp_fill(lp, 0, ln.n192, 0, ln.n192, st) : hipSuccess;
     if (e != hipSuccess) return e;
     e = launch_zero(lp.cnt, sizeof(int) * (size_t)(lp.K + 1), st);
     if (e != hipSuccess) return e;
@@ -2146,8 +1574,7 @@ hipError_t launch_loudnorm(const LnArgs &ln, const LpArgs &lp, const uint32_t *x
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_lp_seg, dim3(lp.P), dim3(LP_NT), 0, st, lp);
     hipLaunchKernelGGL(k_lp_walk, dim3(1), dim3(LP_NT), 0, st, lp);
-    hipLaunchKernelGGL(k_ln_dyn, dim3(1), dim3(LN_NT), 0, st, ln, 1);
-    return hipGetLastError();
+    return launch_ln_dyn(ln, 2, 1, st);
 }
 
 // a chunk-sharded track's share of one filter run (amx_loudnorm_192k_shard), in three
@@ -2179,7 +1606,7 @@ hipError_t launch_loudnorm_shard(const LnArgs &ln, const LpArgs &lp, const uint3
     } else {
         // part 3 (rank 0 of a quiet start): the frames in order from the track start until
         // the hand-over segment (k_ln_dyn phase 0, bounded by ln.lp_tstop)
-        hipLaunchKernelGGL(k_ln_dyn, dim3(1), dim3(LN_NT), 0, st, ln, 0);
+        return launch_ln_dyn(ln, 2, 0, st);
     }
     return hipGetLastError();
 }

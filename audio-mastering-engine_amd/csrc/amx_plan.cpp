@@ -409,7 +409,7 @@ LnLayout ln_layout(int64_t n192, int64_t u_frames = -1, int p_cap = -1) {
     int64_t o = 0;
     auto take = [&](int64_t bytes) { const int64_t at = o; o += ((bytes + 255) / 256) * 256; return at; };
     l.o_u = take((u_frames < 0 ? n192 : u_frames) * 2 * (int64_t)sizeof(float));
-    l.o_ring = take((2 * 40320 + 64) * (int64_t)sizeof(double));
+    l.o_ring = take(AMX_LN_MC_RING(2) * (int64_t)sizeof(double));
     l.o_ctl = take(16 * sizeof(int));
     l.o_dctl = take(8 * sizeof(double));
     l.o_v = take((int64_t)l.T * sizeof(double));
@@ -537,6 +537,20 @@ int amx_loudnorm_192k_size(const amx_plan *p, int32_t track, int64_t *frames, in
 }  // extern "C"
 
 namespace {
+// af_loudnorm init / config_input for k_ln_dyn: the tables, the dB options as the linear
+// factors it keeps, the Gaussian weights and the K filter at 192 kHz
+void ln_options(const amx_plan *p, const amx_loudnorm_desc *d, amx::LnArgs &a) {
+    a.energies = p->d_energies;
+    a.bounds = p->d_bounds;
+    a.target_i = d->target_i;
+    a.target_lra = d->target_lra;
+    a.target_tp = std::pow(10., d->target_tp / 20.);
+    a.measured_i = d->measured_i;
+    a.measured_thresh = d->measured_thresh;
+    a.offset = std::pow(10., d->offset / 20.);
+    ln_gaussian_weights(a.weights);
+    for (int k = 0; k < 5; k++) { a.kb[k] = p->kdf_b[k]; a.ka[k] = p->kdf_a[k]; }
+}
 // the kernels' arguments of one filter run of track `track` (amx_loudnorm_192k_ex / _shard)
 int ln_args(amx_plan *p, int32_t track, const amx_loudnorm_desc *d, const double *d_measured,
             const double *d_offset_i, const int32_t *d_gate, const int16_t *d_out, const double *d_hops,
@@ -565,17 +579,7 @@ int ln_args(amx_plan *p, int32_t track, const amx_loudnorm_desc *d, const double
     a.summary = d_summary;
     a.hops = d_hops + (int64_t)track * max_hops * 2;
     a.peak = d_peak + (int64_t)track * 4;
-    a.energies = p->d_energies;
-    a.bounds = p->d_bounds;
-    // af_loudnorm init / config_input: dB options to the linear factors it keeps
-    a.target_i = d->target_i;
-    a.target_lra = d->target_lra;
-    a.target_tp = std::pow(10., d->target_tp / 20.);
-    a.measured_i = d->measured_i;
-    a.measured_thresh = d->measured_thresh;
-    a.offset = std::pow(10., d->offset / 20.);
-    ln_gaussian_weights(a.weights);
-    for (int k = 0; k < 5; k++) { a.kb[k] = p->kdf_b[k]; a.ka[k] = p->kdf_a[k]; }
+    ln_options(p, d, a);
     q = amx::LpArgs{};
     q.n = n192;
     q.S0 = n192 - (LN_FIRST_FRAMES - 19200);
@@ -1370,26 +1374,16 @@ int amx_mc_loudnorm_192k(amx_plan *p, int32_t channels, const amx_loudnorm_desc 
     const int P = (channels + 1) / 2;
     const int64_t plane = ln_mc_plane_bytes(n192);
     char *w = reinterpret_cast<char *>(d_ws);
-    amx::LnMcArgs a{};
+    amx::LnArgs a{};
     a.n192 = n192;
-    a.u = reinterpret_cast<const float *>(w);
+    a.u = reinterpret_cast<float *>(w);
     a.plane = plane / (int64_t)sizeof(float);
     a.ring = reinterpret_cast<double *>(w + (int64_t)P * plane);
     a.y = d_y192;
     a.summary = d_summary;
     a.hops = d_hops1;
     a.peak = d_peak1;
-    a.energies = p->d_energies;
-    a.bounds = p->d_bounds;
-    // af_loudnorm init / config_input: dB options to the linear factors it keeps
-    a.target_i = d->target_i;
-    a.target_lra = d->target_lra;
-    a.target_tp = std::pow(10., d->target_tp / 20.);
-    a.measured_i = d->measured_i;
-    a.measured_thresh = d->measured_thresh;
-    a.offset = std::pow(10., d->offset / 20.);
-    ln_gaussian_weights(a.weights);
-    for (int k = 0; k < 5; k++) { a.kb[k] = p->kdf_b[k]; a.ka[k] = p->kdf_a[k]; }
+    ln_options(p, d, a);
     hipStream_t st = (hipStream_t)stream;
     if (d->reuse_stream == 0) {
         // each channel pair through the stereo upsampler into its plane
@@ -1400,7 +1394,7 @@ int amx_mc_loudnorm_192k(amx_plan *p, int32_t channels, const amx_loudnorm_desc 
                                            n192, reinterpret_cast<float *>(w + (int64_t)t * plane), nullptr, st));
         }
     }
-    HIPCHK(amx::launch_mc_loudnorm(a, channels, st));
+    HIPCHK(amx::launch_ln_dyn(a, channels, 0, st));
     return AMX_OK;
 }
 

@@ -492,7 +492,7 @@ void Builder::kw_coefficients() {
         cd.kw2[3 + k] = ra[k];
     }
     // the fused direct form itself, for the one place that runs libebur128's filter
-    // sample by sample (loudnorm's r128_out, amx_loudnorm.hip)
+    // sample by sample (loudnorm's r128_out, amx_ln_dyn.hip)
     p->kdf_b[0] = pb[0] * rb[0];
     p->kdf_b[1] = pb[0] * rb[1] + pb[1] * rb[0];
     p->kdf_b[2] = pb[0] * rb[2] + pb[1] * rb[1] + pb[2] * rb[0];

@@ -645,7 +645,8 @@ AMX_API int amx_mc_limiter_out(const amx_plan *plan, const amx_final_desc *fd, c
                                const double *d_att, int16_t *d_out, void *stream);
 /* (ABI 6, added without a layout change) af_loudnorm's 192 kHz modes (dynamic, or the
  * < 3 s linear fallback) on one track of channels = 3..8, frame by frame on one workgroup
- * (DESIGN.md 3.9).  pairs_plan: the stereo measure plan whose ceil(C/2) equal whole tracks
+ * (k_ln_dyn<C>, the kernel a stereo track's quiet start runs in).
+ * pairs_plan: the stereo measure plan whose ceil(C/2) equal whole tracks
  * hold the channel pairs (amx_mc_split_pairs), d_pairs its `out`.  d_hops1 [max_hops][2] /
  * d_peak1 [4]: the track's combined hop energies and peaks (amx_mc_loudness_combine).
  * desc: the options and pass 2's measured values / offset as host numbers; reuse_stream

@@ -1,5 +1,5 @@
 """Time loudnorm's dynamic mode on a multichannel track (MultiChannelJob.dynamic, DESIGN.md
-3.9): the frame-by-frame kernel k_ln_dyn_mc<C> and the steps around it.
+3.9): the frame-by-frame kernel k_ln_dyn<C> and the steps around it.
 
 The case: C = 6, 5 minutes at 48 kHz, synth.mix_like * 0.12 with 50-sample full-scale
 bursts twice a second (the tests' signal), which loudnorm sends to dynamic mode.  One

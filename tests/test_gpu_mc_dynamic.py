@@ -1,5 +1,5 @@
 """loudnorm's dynamic mode on 3..8-channel tracks (the settings key multichannel_dynamic):
-k_ln_dyn_mc<C> through amx_mc_loudnorm_192k, MultiChannelJob.dynamic and the drop-in,
+k_ln_dyn<C> through amx_mc_loudnorm_192k, MultiChannelJob.dynamic and the drop-in,
 against the oracle's restatement of af_loudnorm for any channel count (oracle/amx_oracle.c
 orc_loudnorm; parity unpinned: no ffmpeg here).
 
