@@ -24,7 +24,7 @@ SOURCES = ["amx_chain.hip", "amx_scan.hip", "amx_dyn.hip", "amx_loud.hip", "amx_
            "amx_loudnorm.hip", "amx_ln_dyn.hip", "amx_flacenc.hip", "amx_flacdec.hip", "amx_resample.hip",
            "amx_plan.cpp", "amx_plan_build.cpp", "amx_flac.cpp"]
 HEADERS = ["amx_internal.hpp", "amx_dev.hpp", "amx_tables.hpp", "amx_plan_build.hpp", "amx_plan.hpp",
-           "amx_flacdec_core.hpp", "amx_ln_dev.hpp"]
+           "amx_flacdec_core.hpp", "amx_ln_dev.hpp", "amx_swr_dev.hpp"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
          "-fvisibility=hidden", "-ffp-contract=off", "-Wall", "-Wno-unused-function"]
 

@@ -161,7 +161,7 @@ struct UpArgs {
     int64_t n_slow;
     const float *bank;            // [pc + 1][alloc] float32 polyphase bank (row pc = row 0 one tap on)
     int taps, alloc;              // filter_length, filter_alloc: 32, 32 but for downsampling rates
-                                  // (then every segment goes through k_up_wide)
+                                  // (then every segment goes through k_up_wave<true>)
     const uint32_t *x, *edge;     // d_out (stereo s16 dwords); edge [tracks][2][AMX_UP_EDGE]
     const double *G;              // rows C A^n, n < Lout (the K filter's free response)
     const double *qh, *qt;        // Gram matrices of those rows: head sums [Lout+1][16], tail sums

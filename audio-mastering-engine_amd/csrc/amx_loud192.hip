@@ -4,7 +4,8 @@
 // ffmpeg inserts libswresample with its defaults).  The 192 kHz stream is never
 // materialised: every kernel recomputes the samples it needs from the s16 track.
 //
-// Resampler (restated in oracle/amx_oracle.c, "libswresample"): exact-rational
+// Resampler (restated in oracle/amx_oracle.c, "libswresample"; the device's copy of its
+// arithmetic is amx_swr_dev.hpp, shared with the other resampling kernels): exact-rational
 // polyphase FIR, L phases, step M input samples per L outputs (48 kHz: L 4, M 1;
 // 96 kHz: 2, 1; 44.1 kHz: 640, 147), 32 Kaiser-windowed taps, float32 bank and float32
 // arithmetic (s16 in + dbl out -> FLTP internal format).  Output j = dot of the bank
@@ -35,29 +36,14 @@
 // M == 1 rates (48, 96, 32 kHz ...) take the unrolled path STATIC = L: every input
 // frame has outputs at phases 0 .. L-1 and phase 0 is the identity (the bank's
 // phase-0 row is a unit impulse: u = x exactly).
-#include "amx_dev.hpp"
+#include "amx_swr_dev.hpp"
 
 namespace amx {
 
-#define UP_TAPS 32
-#define UP_C 15            // center tap
 #define AMX_UP_TB 8        // input frames per window block (STATIC path)
 #define AMX_UP_SB 6        // sched_barrier mask: VALU + SALU may cross, scalar loads may not
-#define UP_DOT up_dot2      // packed-pair form of the fast kernel's dot products
+#define UP_DOT swr_dot32_pk // packed-pair form of the fast kernels' dot products
 #define AMX_UP_WAVES 4     // waves per SIMD the register budget must allow
-
-__device__ __forceinline__ float up_sample(uint32_t w, int ch) {
-    return (float)(ch ? hi16(w) : lo16(w)) * (1.0f / 32768.0f);
-}
-
-__device__ __forceinline__ int64_t up_reflect(int64_t k, int64_t n) {
-    for (int it = 0; it < 64; it++) {
-        if (k < 0) k = -k;
-        else if (k >= n) k = 2 * n - 1 - k;
-        else return k;
-    }
-    return 0;
-}
 
 // span-local input frame g of the stream the resampler sees
 __device__ __forceinline__ uint32_t up_word(const uint32_t *__restrict__ x,
@@ -67,41 +53,35 @@ __device__ __forceinline__ uint32_t up_word(const uint32_t *__restrict__ x,
     if (g >= 0 && g < n) return x[sp.out_off + g];
     if (g < 0 && sp.edge_lo && g >= -AMX_UP_EDGE) return edge[((int64_t)t * 2) * AMX_UP_EDGE + AMX_UP_EDGE + g];
     if (g >= n && sp.edge_hi && g < n + AMX_UP_EDGE) return edge[((int64_t)t * 2 + 1) * AMX_UP_EDGE + (g - n)];
-    return n > 0 ? x[sp.out_off + up_reflect(g, n)] : 0u;
+    return n > 0 ? x[sp.out_off + swr_reflect(g, n)] : 0u;
 }
 
-typedef float up_f2 __attribute__((ext_vector_type(2)));
-
-// the FMA3 kernel's order with the 8 chains as 4 packed pairs (v_pk_fma_f32 / v_pk_add_f32):
-// the same operations, lane by lane, as up_dot
-__device__ __forceinline__ float up_dot2(const float *w, const float *__restrict__ h) {
-    up_f2 a[4];
+// the K filter's two sections as bq_step / hp_step read them (b0 b1 b2 a1 a2)
+__device__ __forceinline__ void kw_coefs(const ChainDev *cd, double *c1, double *c2) {
 #pragma unroll
-    for (int k = 0; k < 8; k += 2) {
-        up_f2 acc = up_f2{w[k], w[k + 1]} * up_f2{h[k], h[k + 1]};
-        acc = __builtin_elementwise_fma(up_f2{w[k + 8], w[k + 9]}, up_f2{h[k + 8], h[k + 9]}, acc);
-        acc = __builtin_elementwise_fma(up_f2{w[k + 16], w[k + 17]}, up_f2{h[k + 16], h[k + 17]}, acc);
-        acc = __builtin_elementwise_fma(up_f2{w[k + 24], w[k + 25]}, up_f2{h[k + 24], h[k + 25]}, acc);
-        a[k >> 1] = acc;
-    }
-    const up_f2 b01 = a[0] + a[2], b23 = a[1] + a[3];     // (a0+a4, a1+a5), (a2+a6, a3+a7)
-    const up_f2 c = b01 + b23;                            // (b0+b2, b1+b3)
-    return c.x + c.y;
+    for (int i = 0; i < 3; i++) { c1[i] = cd->kw1[i]; c2[i] = cd->kw2[i]; }
+    c1[3] = cd->kw1[4]; c1[4] = cd->kw1[5];
+    c2[3] = cd->kw2[4]; c2[4] = cd->kw2[5];
 }
 
-// the FMA3 kernel's order
-__device__ __forceinline__ float up_dot(const float *w, const float *__restrict__ h) {
-    float a[8];
-#pragma unroll
-    for (int k = 0; k < 8; k++) {
-        float acc = w[k] * h[k];
-        acc = fmaf(w[k + 8], h[k + 8], acc);
-        acc = fmaf(w[k + 16], h[k + 16], acc);
-        acc = fmaf(w[k + 24], h[k + 24], acc);
-        a[k] = acc;
-    }
-    const float b0 = a[0] + a[4], b1 = a[1] + a[5], b2 = a[2] + a[6], b3 = a[3] + a[7];
-    return (b0 + b2) + (b1 + b3);
+// K segment j: its span, first input frame within the span, the outputs before the next
+// 100 ms hop boundary (piece 0: outputs [0, split), piece 1 the rest) and its outputs
+struct UpSeg {
+    KwSegDev sg;
+    SpanDev sp;
+    int t;
+    int64_t g0, split;
+    int len;
+};
+__device__ __forceinline__ UpSeg up_seg(const UpArgs &a, int64_t j) {
+    UpSeg s;
+    s.sg = a.ks[j];
+    s.sp = a.spans[s.sg.track];
+    s.t = s.sg.track;
+    s.g0 = s.sg.out_pos - s.sp.out_off;
+    s.split = (s.sg.tframe / a.hop + 1) * a.hop - s.sg.tframe;          // 1 .. hop
+    s.len = s.sg.len;
+    return s;
 }
 
 // libebur128's second K section, the RLB high-pass: b = (1, -2, 1) always, so the
@@ -170,11 +150,11 @@ template <int STATIC>
 __device__ __forceinline__ void up_run_fast(const UpArgs &a, const SpanDev &sp, int ch, int64_t g0,
                                             bool vec, const int *zp, UpAcc<true> &acc) {
     constexpr int TB = AMX_UP_TB;
-    constexpr int W = TB + UP_TAPS - 1;                        // inputs [k0 - 15, k0 + TB + 16)
+    constexpr int W = TB + SWR_TAPS - 1;                        // inputs [k0 - 15, k0 + TB + 16)
     float w[W];
-    const uint32_t *xp = a.x + sp.out_off + g0 - UP_C;         // frame g0 - 15
+    const uint32_t *xp = a.x + sp.out_off + g0 - SWR_C;         // frame g0 - 15
 #pragma unroll
-    for (int i = 0; i < W; i++) w[i] = up_sample(xp[i], ch);
+    for (int i = 0; i < W; i++) w[i] = swr_tap(xp[i], ch);
     const int nblk = a.Lin / TB;
     for (int b = 0; b < nblk; b++) {
         // next block's new frames in flight while this block computes (past the last
@@ -200,27 +180,24 @@ __device__ __forceinline__ void up_run_fast(const UpArgs &a, const SpanDev &sp, 
             // block's rows would not fit the SGPRs
             __builtin_amdgcn_sched_barrier(AMX_UP_SB);
             const int n0 = nb0 + kb * STATIC;
-            acc.add(n0, w[kb + UP_C], w[kb + UP_C]);
+            acc.add(n0, w[kb + SWR_C], w[kb + SWR_C]);
 #pragma unroll
             for (int ph = 1; ph < STATIC; ph++) {
                 __builtin_amdgcn_sched_barrier(AMX_UP_SB);
-                acc.add(n0 + ph, UP_DOT(w + kb, bk + ph * UP_TAPS), w[kb + UP_C]);
+                acc.add(n0 + ph, UP_DOT(w + kb, bk + ph * SWR_TAPS), w[kb + SWR_C]);
             }
         }
         __builtin_amdgcn_sched_barrier(AMX_UP_SB);
 #pragma unroll
         for (int i = 0; i < W - TB; i++) w[i] = w[i + TB];
 #pragma unroll
-        for (int i = 0; i < TB; i++) w[W - TB + i] = up_sample(nx[i], ch);
+        for (int i = 0; i < TB; i++) w[W - TB + i] = swr_tap(nx[i], ch);
     }
 }
 
 template <class Acc>
 __device__ __forceinline__ void acc_init(const UpArgs &a, Acc &acc, int split, int len) {
-#pragma unroll
-    for (int i = 0; i < 3; i++) { acc.c1[i] = a.cd->kw1[i]; acc.c2[i] = a.cd->kw2[i]; }
-    acc.c1[3] = a.cd->kw1[4]; acc.c1[4] = a.cd->kw1[5];
-    acc.c2[3] = a.cd->kw2[4]; acc.c2[4] = a.cd->kw2[5];
+    kw_coefs(a.cd, acc.c1, acc.c2);
 #pragma unroll
     for (int d = 0; d < 4; d++) { acc.v[d] = 0.0; acc.q0[d] = 0.0; acc.q1[d] = 0.0; }
     acc.z0 = acc.z1 = 0.0;
@@ -230,14 +207,20 @@ __device__ __forceinline__ void acc_init(const UpArgs &a, Acc &acc, int split, i
     acc.wc = a.G;
 }
 
-template <class Acc>
-__device__ __forceinline__ void acc_store(const UpArgs &a, const Acc &acc, int64_t j, int ch) {
+// segment j, channel ch: the K filter's end state from rest and the sample peaks
+__device__ __forceinline__ void up_state_store(const UpArgs &a, int64_t j, int ch, const double *v, float pk,
+                                               float px) {
     double *o = a.e + (j * 2 + ch) * AMX_KW_DIM;
 #pragma unroll
-    for (int d = 0; d < AMX_KW_DIM; d++) o[d] = acc.v[d];
+    for (int d = 0; d < AMX_KW_DIM; d++) o[d] = v[d];
     uint32_t *q = a.pk + j * 4;
-    q[ch] = __float_as_uint(acc.pk);
-    q[2 + ch] = (uint32_t)(acc.px * 32768.0f);      // |s16| / 32768: exact
+    q[ch] = __float_as_uint(pk);
+    q[2 + ch] = (uint32_t)(px * 32768.0f);          // |s16| / 32768: exact
+}
+
+template <class Acc>
+__device__ __forceinline__ void acc_store(const UpArgs &a, const Acc &acc, int64_t j, int ch) {
+    up_state_store(a, j, ch, acc.v, acc.pk, acc.px);
     // energy terms: [piece][sum yz^2, sum yz (C A^n)^T (4)]
     double *t = a.eterms + (j * 2 + ch) * 10;
     t[0] = acc.z0;
@@ -246,58 +229,87 @@ __device__ __forceinline__ void acc_store(const UpArgs &a, const Acc &acc, int64
     for (int d = 0; d < 4; d++) { t[1 + d] = acc.q0[d]; t[6 + d] = acc.q1[d]; }
 }
 
-__device__ __forceinline__ bool up_fast_seg(const UpArgs &a, const KwSegDev &sg, const SpanDev &sp) {
-    const int64_t g0 = sg.out_pos - sp.out_off;
-    const int64_t h0 = sg.tframe / a.hop;
-    const int64_t split = (h0 + 1) * a.hop - sg.tframe;
-    return g0 - UP_C >= 0 && g0 + a.Lin + UP_TAPS - UP_C <= sp.out_n && sg.len == a.Lout &&
-           split >= a.Lout;
+__device__ __forceinline__ bool up_fast_seg(const UpArgs &a, const UpSeg &s) {
+    return s.g0 - SWR_C >= 0 && s.g0 + a.Lin + SWR_TAPS - SWR_C <= s.sp.out_n && s.len == a.Lout &&
+           s.split >= a.Lout;
 }
 
-// k_up_edge's work in chunks of AMX_UPE_CH outputs, for the first workgroups of k_up
+// ------------------------------------------------------------ one wave per segment
+// The pieces k_up_wave and up_edge_chunked (below) share.  A lane accumulates the energy
+// terms of the outputs it is given, both channels: acc[ch][piece][sum y^2, sum y (C A^n)^T].
+// y: output n's K-filtered samples [ch]
+__device__ __forceinline__ void up_terms_add(double (&acc)[2][2][5], int n, int split, const double *y,
+                                             const double *G) {
+    const double *r = G + (int64_t)n * AMX_KW_DIM;
+    const int pc = n < split ? 0 : 1;
+#pragma unroll
+    for (int c = 0; c < 2; c++)
+#pragma unroll
+        for (int p = 0; p < 2; p++) {
+            const double yy = p == pc ? y[c] : 0.0;
+            acc[c][p][0] = fma(yy, yy, acc[c][p][0]);
+#pragma unroll
+            for (int d = 0; d < 4; d++) acc[c][p][1 + d] = fma(yy, r[d], acc[c][p][1 + d]);
+        }
+}
+
+// the lanes' terms summed over the wave; lanes 0 / 1 store channel ch = lane's
+__device__ __forceinline__ void up_terms_reduce_store(const UpArgs &a, int64_t j, int ch, double (&acc)[2][2][5]) {
+#pragma unroll
+    for (int c = 0; c < 2; c++)
+#pragma unroll
+        for (int p = 0; p < 2; p++)
+#pragma unroll
+            for (int k = 0; k < 5; k++) {
+                double x = acc[c][p][k];
+#pragma unroll
+                for (int o = 1; o < 64; o <<= 1) x += __shfl_xor(x, o);
+                acc[c][p][k] = x;
+            }
+    if ((threadIdx.x & 63) < 2) {
+        double *te = a.eterms + (j * 2 + ch) * 10;
+#pragma unroll
+        for (int p = 0; p < 2; p++)
+#pragma unroll
+            for (int k = 0; k < 5; k++) te[p * 5 + k] = ch ? acc[1][p][k] : acc[0][p][k];
+    }
+}
+
+// k_up_wave<false>'s work in chunks of AMX_UPE_CH outputs, for the first workgroups of k_up
 // (below): a left-over segment's frames in LDS, the resampled samples and the K filter's
-// outputs of one chunk at a time (5 KB instead of k_up_edge's 12 KB, so the fast
-// kernel's own workgroups keep their occupancy).  Every sum keeps k_up_edge's order:
+// outputs of one chunk at a time (5 KB instead of k_up_wave's 12 KB, so the fast
+// kernel's own workgroups keep their occupancy).  Every sum keeps k_up_wave's order:
 // lane l still accumulates outputs l, l + 64, ... in turn (chunks are multiples of 64),
-// and the K filter runs on, serially, from chunk to chunk.  A k_up_edge beside k_up
+// and the K filter runs on, serially, from chunk to chunk.  A k_up_wave beside k_up
 // needed a fork and a join in the step's graph; the join alone cost ~10 us.
 #define AMX_UPE_CH 128
 #define AMX_UPE_NF 544            // frames staged: Lin + 32 <= 544 (static paths: Lin <= 480)
 __device__ __forceinline__ void up_edge_chunked(const UpArgs &a, int64_t j, uint32_t *fr, float *us,
                                                 double *ys) {
     const int lane = threadIdx.x & 63;
-    const KwSegDev sg = a.ks[j];
-    const SpanDev sp = a.spans[sg.track];
-    const int t = sg.track;
-    const int64_t g0 = sg.out_pos - sp.out_off;
-    const int nf = a.Lin + UP_TAPS;                               // frames g0 - 15 + [0, nf)
-    for (int i = lane; i < nf; i += 64) fr[i] = up_word(a.x, a.edge, sp, t, g0 - UP_C + i);
+    const UpSeg s = up_seg(a, j);
+    const int nf = a.Lin + SWR_TAPS;                              // frames g0 - 15 + [0, nf)
+    for (int i = lane; i < nf; i += 64) fr[i] = up_word(a.x, a.edge, s.sp, s.t, s.g0 - SWR_C + i);
     __syncthreads();
-    const int len = sg.len;
     const int ch = lane & 1;
     float pk = 0.0f, px = 0.0f;
     double c1[5], c2[5];
-#pragma unroll
-    for (int k = 0; k < 3; k++) { c1[k] = a.cd->kw1[k]; c2[k] = a.cd->kw2[k]; }
-    c1[3] = a.cd->kw1[4]; c1[4] = a.cd->kw1[5];
-    c2[3] = a.cd->kw2[4]; c2[4] = a.cd->kw2[5];
+    kw_coefs(a.cd, c1, c2);
     double v[4] = {0.0, 0.0, 0.0, 0.0};
-    const int64_t h0 = sg.tframe / a.hop;
-    const int split = (int)((h0 + 1) * a.hop - sg.tframe);
-    double acc[2][2][5] = {};                                     // [ch][piece][term]
+    double acc[2][2][5] = {};
     for (int n0 = 0; n0 < a.Lout; n0 += AMX_UPE_CH) {
         const int nc = a.Lout - n0 < AMX_UPE_CH ? a.Lout - n0 : AMX_UPE_CH;
         for (int i = lane; i < 2 * nc; i += 64) {                 // i & 1 == ch
             const int n = n0 + (i >> 1);
             const int kb = a.obase[n], ph = a.oph[n];
-            float w[UP_TAPS];
+            float w[SWR_TAPS];
 #pragma unroll
-            for (int k = 0; k < UP_TAPS; k++) w[k] = up_sample(fr[kb + k], ch);
-            const float u = (a.static_l > 0 && ph == 0) ? w[UP_C] : up_dot(w, a.bank + ph * UP_TAPS);
+            for (int k = 0; k < SWR_TAPS; k++) w[k] = swr_tap(fr[kb + k], ch);
+            const float u = (a.static_l > 0 && ph == 0) ? w[SWR_C] : swr_dot32(w, a.bank + ph * SWR_TAPS);
             us[i] = u;
-            if (n < len) {
+            if (n < s.len) {
                 pk = fmaxf(pk, fabsf(u));
-                px = fmaxf(px, fabsf(w[UP_C]));
+                px = fmaxf(px, fabsf(w[SWR_C]));
             }
         }
         __syncthreads();
@@ -305,28 +317,13 @@ __device__ __forceinline__ void up_edge_chunked(const UpArgs &a, int64_t j, uint
         if (lane < 2) {
             for (int k = 0; k < nc; k++) {
                 const int n = n0 + k;
-                ys[2 * k + ch] = n < len ? hp_step(c2, v[2], v[3], bq_step(c1, v[0], v[1], (double)us[2 * k + ch]))
-                                         : 0.0;
+                ys[2 * k + ch] = n < s.len ? hp_step(c2, v[2], v[3], bq_step(c1, v[0], v[1], (double)us[2 * k + ch]))
+                                           : 0.0;
             }
         }
         __syncthreads();
-        for (int k = lane; k < nc; k += 64) {
-            const int n = n0 + k;
-            if (n >= len) continue;
-            const double *r = a.G + (int64_t)n * AMX_KW_DIM;
-            const int pc = n < split ? 0 : 1;
-#pragma unroll
-            for (int c = 0; c < 2; c++) {
-                const double y = ys[2 * k + c];
-#pragma unroll
-                for (int q = 0; q < 2; q++) {
-                    const double yy = q == pc ? y : 0.0;
-                    acc[c][q][0] = fma(yy, yy, acc[c][q][0]);
-#pragma unroll
-                    for (int d = 0; d < 4; d++) acc[c][q][1 + d] = fma(yy, r[d], acc[c][q][1 + d]);
-                }
-            }
-        }
+        for (int k = lane; k < nc; k += 64)
+            if (n0 + k < s.len) up_terms_add(acc, n0 + k, (int)s.split, ys + 2 * k, a.G);
         __syncthreads();                                          // us / ys are rewritten next chunk
     }
 #pragma unroll
@@ -334,30 +331,8 @@ __device__ __forceinline__ void up_edge_chunked(const UpArgs &a, int64_t j, uint
         pk = fmaxf(pk, __shfl_xor(pk, o));
         px = fmaxf(px, __shfl_xor(px, o));
     }
-#pragma unroll
-    for (int c = 0; c < 2; c++)
-#pragma unroll
-        for (int q = 0; q < 2; q++)
-#pragma unroll
-            for (int k = 0; k < 5; k++) {
-                double x = acc[c][q][k];
-#pragma unroll
-                for (int o = 1; o < 64; o <<= 1) x += __shfl_xor(x, o);
-                acc[c][q][k] = x;
-            }
-    if (lane < 2) {
-        double *o = a.e + (j * 2 + ch) * AMX_KW_DIM;
-#pragma unroll
-        for (int d = 0; d < AMX_KW_DIM; d++) o[d] = v[d];
-        uint32_t *pq = a.pk + j * 4;
-        pq[ch] = __float_as_uint(pk);
-        pq[2 + ch] = (uint32_t)(px * 32768.0f);
-        double *te = a.eterms + (j * 2 + ch) * 10;
-#pragma unroll
-        for (int q = 0; q < 2; q++)
-#pragma unroll
-            for (int k = 0; k < 5; k++) te[q * 5 + k] = ch ? acc[1][q][k] : acc[0][q][k];
-    }
+    up_terms_reduce_store(a, j, ch, acc);
+    if (lane < 2) up_state_store(a, j, ch, v, pk, px);
 }
 
 // one lane per (segment, channel); lanes of segments k_up_slow owns return at once
@@ -378,15 +353,13 @@ k_up(UpArgs a, int n_edge) {
     const int ch = lane & 1;
     const int64_t j = (int64_t)(blockIdx.x - n_edge) * (AMX_UP_BLOCK / 2) + (lane >> 1);
     if (j >= a.n_kseg) return;
-    const KwSegDev sg = a.ks[j];
-    const SpanDev sp = a.spans[sg.track];
-    if (!up_fast_seg(a, sg, sp)) return;
-    const int64_t g0 = sg.out_pos - sp.out_off;
+    const UpSeg s = up_seg(a, j);
+    if (!up_fast_seg(a, s)) return;
     // 16-B loads when every lane's window rows are 16-B aligned
-    const bool vec = __ballot(((sp.out_off + g0 - UP_C + (UP_TAPS - 1)) & 3) != 0) == 0;
+    const bool vec = __ballot(((s.sp.out_off + s.g0 - SWR_C + (SWR_TAPS - 1)) & 3) != 0) == 0;
     UpAcc<true> acc;
     acc_init(a, acc, a.Lout, a.Lout);
-    up_run_fast<STATIC>(a, sp, ch, g0, vec, zp, acc);
+    up_run_fast<STATIC>(a, s.sp, ch, s.g0, vec, zp, acc);
     acc_store(a, acc, j, ch);
 }
 
@@ -398,7 +371,7 @@ k_up(UpArgs a, int n_edge) {
 // order (bankn[n] = bank[oph[n]]): a scalar load at an address the output counter gives,
 // where k_up_slow first loads obase[n] and oph[n] and only then the row, and moves its
 // window one frame at a time through masked, bounds-tested loads.  The segments this
-// kernel leaves (span ends, partial segments, hop splits) go to k_up_edge, as for k_up.
+// kernel leaves (span ends, partial segments, hop splits) go to k_up_wave<false>, as for k_up.
 template <int CMIN, int CMAX, int TB>
 __global__ void __launch_bounds__(AMX_UP_BLOCK) __attribute__((amdgpu_waves_per_eu(AMX_UP_WAVES)))
 k_up_poly(UpArgs a) {
@@ -407,26 +380,24 @@ k_up_poly(UpArgs a) {
     const int ch = lane & 1;
     const int64_t j = (int64_t)blockIdx.x * (AMX_UP_BLOCK / 2) + (lane >> 1);
     if (j >= a.n_kseg) return;
-    const KwSegDev sg = a.ks[j];
-    const SpanDev sp = a.spans[sg.track];
-    if (!up_fast_seg(a, sg, sp)) return;
-    const int64_t g0 = sg.out_pos - sp.out_off;
+    const UpSeg s = up_seg(a, j);
+    if (!up_fast_seg(a, s)) return;
     UpAcc<true> acc;
     acc_init(a, acc, a.Lout, a.Lout);
-    constexpr int W = TB + UP_TAPS - 1;                        // inputs [k0 - 15, k0 + TB + 16)
+    constexpr int W = TB + SWR_TAPS - 1;                        // inputs [k0 - 15, k0 + TB + 16)
     float w[W];
-    const uint32_t *xp = a.x + sp.out_off + g0 - UP_C;         // frame g0 - 15
+    const uint32_t *xp = a.x + s.sp.out_off + s.g0 - SWR_C;     // frame g0 - 15
 #pragma unroll
-    for (int i = 0; i < W; i++) w[i] = up_sample(xp[i], ch);
+    for (int i = 0; i < W; i++) w[i] = swr_tap(xp[i], ch);
     const int nblk = a.Lin / TB;
     int n = 0;                                                 // next output (wave-uniform)
     // the rows of output n (bank row, C A^n row) are loaded while output n - 1 computes:
     // 40 scalar registers in flight instead of a scalar-cache miss on every output (the
     // 640 rows of 44.1 kHz are 80 KB)
-    float h[UP_TAPS];
+    float h[SWR_TAPS];
     double r[AMX_KW_DIM];
 #pragma unroll
-    for (int i = 0; i < UP_TAPS; i++) h[i] = a.bankn[i];
+    for (int i = 0; i < SWR_TAPS; i++) h[i] = a.bankn[i];
 #pragma unroll
     for (int d = 0; d < AMX_KW_DIM; d++) r[d] = a.G[d];
     for (int b = 0; b < nblk; b++) {
@@ -443,17 +414,17 @@ k_up_poly(UpArgs a) {
                 if (o < CMIN || o < c) {
                     __builtin_amdgcn_sched_barrier(AMX_UP_SB);
                     const int nn = n + 1 < a.Lout ? n + 1 : n;
-                    float hn[UP_TAPS];
+                    float hn[SWR_TAPS];
                     double rn[AMX_KW_DIM];
-                    const float *hp = a.bankn + (int64_t)nn * UP_TAPS;
+                    const float *hp = a.bankn + (int64_t)nn * SWR_TAPS;
                     const double *rp = a.G + (int64_t)nn * AMX_KW_DIM;
 #pragma unroll
-                    for (int i = 0; i < UP_TAPS; i++) hn[i] = hp[i];
+                    for (int i = 0; i < SWR_TAPS; i++) hn[i] = hp[i];
 #pragma unroll
                     for (int d = 0; d < AMX_KW_DIM; d++) rn[d] = rp[d];
-                    acc.add_row(n, UP_DOT(w + kb, h), w[kb + UP_C], r);
+                    acc.add_row(n, UP_DOT(w + kb, h), w[kb + SWR_C], r);
 #pragma unroll
-                    for (int i = 0; i < UP_TAPS; i++) h[i] = hn[i];
+                    for (int i = 0; i < SWR_TAPS; i++) h[i] = hn[i];
 #pragma unroll
                     for (int d = 0; d < AMX_KW_DIM; d++) r[d] = rn[d];
                     n++;
@@ -464,7 +435,7 @@ k_up_poly(UpArgs a) {
 #pragma unroll
         for (int i = 0; i < W - TB; i++) w[i] = w[i + TB];
 #pragma unroll
-        for (int i = 0; i < TB; i++) w[W - TB + i] = up_sample(nx[i], ch);
+        for (int i = 0; i < TB; i++) w[W - TB + i] = swr_tap(nx[i], ch);
     }
     acc_store(a, acc, j, ch);
 }
@@ -479,70 +450,75 @@ __global__ void __launch_bounds__(AMX_UP_BLOCK) k_up_slow(UpArgs a) {
     const int64_t q = (int64_t)blockIdx.x * (AMX_UP_BLOCK / 2) + (lane >> 1);
     if (q >= a.n_slow) return;
     const int64_t j = a.slow ? a.slow[q] : q;
-    const KwSegDev sg = a.ks[j];
-    const SpanDev sp = a.spans[sg.track];
-    const int t = sg.track;
-    const int64_t g0 = sg.out_pos - sp.out_off;
-    const int64_t h0 = sg.tframe / a.hop;
+    const UpSeg s = up_seg(a, j);
     UpAcc<false> acc;
-    acc_init(a, acc, (int)((h0 + 1) * a.hop - sg.tframe), sg.len);
-    float w[UP_TAPS];
-    for (int i = 0; i < UP_TAPS; i++) {
-        const float v = up_sample(up_word(a.x, a.edge, sp, t, g0 - UP_C + i), ch);
+    acc_init(a, acc, (int)s.split, s.len);
+    float w[SWR_TAPS];
+    for (int i = 0; i < SWR_TAPS; i++) {
+        const float v = swr_tap(up_word(a.x, a.edge, s.sp, s.t, s.g0 - SWR_C + i), ch);
 #pragma unroll
-        for (int k = 0; k < UP_TAPS; k++) w[k] = k == i ? v : w[k];
+        for (int k = 0; k < SWR_TAPS; k++) w[k] = k == i ? v : w[k];
     }
     int cur = 0;
     for (int n = 0; n < a.Lout; n++) {
         const int kb = a.obase[n];
         if (kb > cur) {                                         // one frame on
 #pragma unroll
-            for (int i = 0; i < UP_TAPS - 1; i++) w[i] = w[i + 1];
-            w[UP_TAPS - 1] = up_sample(up_word(a.x, a.edge, sp, t, g0 + cur + UP_TAPS - UP_C), ch);
+            for (int i = 0; i < SWR_TAPS - 1; i++) w[i] = w[i + 1];
+            w[SWR_TAPS - 1] = swr_tap(up_word(a.x, a.edge, s.sp, s.t, s.g0 + cur + SWR_TAPS - SWR_C), ch);
             cur++;
         }
         const int ph = a.oph[n];
-        const float u = a.lin ? swr_dot_lin(w, a.bank + ph * UP_TAPS, a.bank + (ph + 1) * UP_TAPS, a.owt[n])
-                        : (a.static_l > 0 && ph == 0) ? w[UP_C] : up_dot(w, a.bank + ph * UP_TAPS);
-        acc.add(n, u, w[UP_C]);
+        const float u = a.lin ? swr_dot_lin(w, a.bank + ph * SWR_TAPS, a.bank + (ph + 1) * SWR_TAPS, a.owt[n])
+                        : (a.static_l > 0 && ph == 0) ? w[SWR_C] : swr_dot32(w, a.bank + ph * SWR_TAPS);
+        acc.add(n, u, w[SWR_C]);
     }
     acc_store(a, acc, j, ch);
 }
 
-// The static path's left-over segments (span ends, partial segments, hop splits: a
-// few per span), one wave per segment: the lane-per-segment form above would run each
-// of them as one serial lane over Lout outputs, all taps and edge tests included --
-// longer than the whole fast kernel.  Here the wave stages the segment's frames in LDS,
-// computes the 2 x Lout resampled samples and the peaks in parallel, and only the K
-// filter recursion (one lane per channel) stays serial.
-__global__ void __launch_bounds__(64) k_up_edge(UpArgs a) {
+// One wave per segment.  WIDE false: the left-over segments of the static and poly paths
+// (span ends, partial segments, hop splits: a few per span, the plan's slow list); the
+// lane-per-segment form above would run each of them as one serial lane over Lout outputs,
+// all taps and edge tests included -- longer than the whole fast kernel.  WIDE true: every
+// K segment of a downsampling rate (an input above 192 kHz / 0.97: 352.8, 384, 705.6, 768
+// kHz; the filter has `taps` > 32 taps in rows of `alloc`; no slow list unless the plan
+// gives one).  The wave stages the segment's frames in LDS from g0 - center, computes the
+// 2 x Lout resampled samples and the peaks in parallel, runs the K filter recursion on one
+// lane per channel, and reduces the energy terms over the wave.  The window of output n is
+// frames obase[n] - center .. + row - 1 (a wide row's zero padding multiplies the frames
+// after it, as the x86 kernel does); a slow list comes only with static_l or poly, which
+// exclude the interpolating rates (Builder::resampler_phases), so no output interpolates.
+template <bool WIDE>
+__global__ void __launch_bounds__(64) k_up_wave(UpArgs a) {
     extern __shared__ uint32_t sh[];
     const int lane = threadIdx.x;
-    const int64_t j = a.slow[blockIdx.x];
-    const KwSegDev sg = a.ks[j];
-    const SpanDev sp = a.spans[sg.track];
-    const int t = sg.track;
-    const int64_t g0 = sg.out_pos - sp.out_off;
-    const int nf = a.Lin + UP_TAPS;                               // frames g0 - 15 + [0, nf)
+    const int64_t j = (WIDE && !a.slow) ? (int64_t)blockIdx.x : a.slow[blockIdx.x];
+    const UpSeg s = up_seg(a, j);
+    const int c = WIDE ? (a.taps - 1) / 2 : SWR_C;
+    const int row = WIDE ? a.alloc : SWR_TAPS;
+    const int nf = a.Lin + row;                                   // frames g0 - c + [0, nf)
     uint32_t *fr = sh;
     float *us = reinterpret_cast<float *>(sh + nf);               // [n][ch]
-    for (int i = lane; i < nf; i += 64) fr[i] = up_word(a.x, a.edge, sp, t, g0 - UP_C + i);
+    for (int i = lane; i < nf; i += 64) fr[i] = up_word(a.x, a.edge, s.sp, s.t, s.g0 - c + i);
     __syncthreads();
-    const int len = sg.len;
     const int ch = lane & 1;
     float pk = 0.0f, px = 0.0f;
     for (int i = lane; i < 2 * a.Lout; i += 64) {                 // i & 1 == ch
         const int n = i >> 1;
         const int kb = a.obase[n], ph = a.oph[n];
-        float w[UP_TAPS];
+        float u;
+        if constexpr (WIDE) {
+            u = swr_dot_rows<float>([&](int k) { return swr_tap(fr[kb + k], ch); }, a.bank + (int64_t)ph * row, 1, row);
+        } else {
+            float w[SWR_TAPS];
 #pragma unroll
-        for (int k = 0; k < UP_TAPS; k++) w[k] = up_sample(fr[kb + k], ch);
-        const float u = a.lin ? swr_dot_lin(w, a.bank + ph * UP_TAPS, a.bank + (ph + 1) * UP_TAPS, a.owt[n])
-                        : (a.static_l > 0 && ph == 0) ? w[UP_C] : up_dot(w, a.bank + ph * UP_TAPS);
+            for (int k = 0; k < SWR_TAPS; k++) w[k] = swr_tap(fr[kb + k], ch);
+            u = (a.static_l > 0 && ph == 0) ? w[SWR_C] : swr_dot32(w, a.bank + ph * SWR_TAPS);
+        }
         us[i] = u;
-        if (n < len) {
+        if (n < s.len) {
             pk = fmaxf(pk, fabsf(u));
-            px = fmaxf(px, fabsf(w[UP_C]));
+            px = fmaxf(px, fabsf(swr_tap(fr[kb + c], ch)));
         }
     }
 #pragma unroll
@@ -555,13 +531,10 @@ __global__ void __launch_bounds__(64) k_up_edge(UpArgs a) {
     double *ys = reinterpret_cast<double *>(sh + ((nf + 2 * a.Lout + 1) & ~1));   // [n][ch]
     if (lane < 2) {
         double c1[5], c2[5];
-#pragma unroll
-        for (int k = 0; k < 3; k++) { c1[k] = a.cd->kw1[k]; c2[k] = a.cd->kw2[k]; }
-        c1[3] = a.cd->kw1[4]; c1[4] = a.cd->kw1[5];
-        c2[3] = a.cd->kw2[4]; c2[4] = a.cd->kw2[5];
+        kw_coefs(a.cd, c1, c2);
         double v[4] = {0.0, 0.0, 0.0, 0.0};
         int n = 0;
-        for (; n + 8 <= len; n += 8) {
+        for (; n + 8 <= s.len; n += 8) {
             float ub[8];
 #pragma unroll
             for (int k = 0; k < 8; k++) ub[k] = us[2 * (n + k) + ch];
@@ -569,166 +542,15 @@ __global__ void __launch_bounds__(64) k_up_edge(UpArgs a) {
             for (int k = 0; k < 8; k++)
                 ys[2 * (n + k) + ch] = hp_step(c2, v[2], v[3], bq_step(c1, v[0], v[1], (double)ub[k]));
         }
-        for (; n < len; n++)
+        for (; n < s.len; n++)
             ys[2 * n + ch] = hp_step(c2, v[2], v[3], bq_step(c1, v[0], v[1], (double)us[2 * n + ch]));
         for (; n < a.Lout; n++) ys[2 * n + ch] = 0.0;
-        double *o = a.e + (j * 2 + ch) * AMX_KW_DIM;
-#pragma unroll
-        for (int d = 0; d < AMX_KW_DIM; d++) o[d] = v[d];
-        uint32_t *pq = a.pk + j * 4;
-        pq[ch] = __float_as_uint(pk);
-        pq[2 + ch] = (uint32_t)(px * 32768.0f);
+        up_state_store(a, j, ch, v, pk, px);
     }
     __syncthreads();
-    // energy terms per hop piece, all lanes: sum y^2, sum y (C A^n)^T
-    const int64_t h0 = sg.tframe / a.hop;
-    const int split = (int)((h0 + 1) * a.hop - sg.tframe);
-    double acc[2][2][5] = {};                                     // [ch][piece][term]
-    for (int n = lane; n < len; n += 64) {
-        const double *r = a.G + (int64_t)n * AMX_KW_DIM;
-        const int pc = n < split ? 0 : 1;
-#pragma unroll
-        for (int c = 0; c < 2; c++) {
-            const double y = ys[2 * n + c];
-#pragma unroll
-            for (int p = 0; p < 2; p++) {
-                const double yy = p == pc ? y : 0.0;
-                acc[c][p][0] = fma(yy, yy, acc[c][p][0]);
-#pragma unroll
-                for (int d = 0; d < 4; d++) acc[c][p][1 + d] = fma(yy, r[d], acc[c][p][1 + d]);
-            }
-        }
-    }
-#pragma unroll
-    for (int c = 0; c < 2; c++)
-#pragma unroll
-        for (int p = 0; p < 2; p++)
-#pragma unroll
-            for (int k = 0; k < 5; k++) {
-                double x = acc[c][p][k];
-#pragma unroll
-                for (int o = 1; o < 64; o <<= 1) x += __shfl_xor(x, o);
-                acc[c][p][k] = x;
-            }
-    if (lane < 2) {
-        double *te = a.eterms + (j * 2 + ch) * 10;
-#pragma unroll
-        for (int p = 0; p < 2; p++)
-#pragma unroll
-            for (int k = 0; k < 5; k++) te[p * 5 + k] = ch ? acc[1][p][k] : acc[0][p][k];
-    }
-}
-
-// the FMA3 kernel's order over a row of `alloc` taps (a multiple of 8: the downsampling
-// filters of inputs above 192 kHz), the window's frames read from LDS: 8 chains over taps
-// k, k + 8, ..., then the common horizontal sum
-__device__ __forceinline__ float up_dot_wide(const uint32_t *fr, int ch, const float *__restrict__ h, int alloc) {
-    float a[8];
-#pragma unroll
-    for (int k = 0; k < 8; k++) {
-        float acc = up_sample(fr[k], ch) * h[k];
-        for (int q = 8; q < alloc; q += 8) acc = fmaf(up_sample(fr[k + q], ch), h[k + q], acc);
-        a[k] = acc;
-    }
-    const float b0 = a[0] + a[4], b1 = a[1] + a[5], b2 = a[2] + a[6], b3 = a[3] + a[7];
-    return (b0 + b2) + (b1 + b3);
-}
-
-// Every K segment of a downsampling rate (an input above 192 kHz / 0.97: 352.8, 384,
-// 705.6, 768 kHz; the filter has `taps` > 32 taps in rows of `alloc`), one wave per
-// segment as k_up_edge: the segment's frames staged in LDS from g0 - center, the 2 x Lout
-// outputs in parallel, the K filter on one lane per channel, the energy terms reduced
-// over the wave.  The window of output n is frames obase[n] - center .. + alloc - 1 (the
-// row's zero padding multiplies the frames after it, as the x86 kernel does).
-__global__ void __launch_bounds__(64) k_up_wide(UpArgs a) {
-    extern __shared__ uint32_t sh[];
-    const int lane = threadIdx.x;
-    const int64_t j = a.slow ? a.slow[blockIdx.x] : (int64_t)blockIdx.x;
-    const KwSegDev sg = a.ks[j];
-    const SpanDev sp = a.spans[sg.track];
-    const int t = sg.track;
-    const int64_t g0 = sg.out_pos - sp.out_off;
-    const int c = (a.taps - 1) / 2;
-    const int nf = a.Lin + a.alloc;                               // frames g0 - c + [0, nf)
-    uint32_t *fr = sh;
-    float *us = reinterpret_cast<float *>(sh + nf);               // [n][ch]
-    for (int i = lane; i < nf; i += 64) fr[i] = up_word(a.x, a.edge, sp, t, g0 - c + i);
-    __syncthreads();
-    const int len = sg.len;
-    const int ch = lane & 1;
-    float pk = 0.0f, px = 0.0f;
-    for (int i = lane; i < 2 * a.Lout; i += 64) {                 // i & 1 == ch
-        const int n = i >> 1;
-        const int kb = a.obase[n], ph = a.oph[n];
-        const float u = up_dot_wide(fr + kb, ch, a.bank + (int64_t)ph * a.alloc, a.alloc);
-        us[i] = u;
-        if (n < len) {
-            pk = fmaxf(pk, fabsf(u));
-            px = fmaxf(px, fabsf(up_sample(fr[kb + c], ch)));
-        }
-    }
-#pragma unroll
-    for (int o = 2; o < 64; o <<= 1) {                            // max over the channel's lanes
-        pk = fmaxf(pk, __shfl_xor(pk, o));
-        px = fmaxf(px, __shfl_xor(px, o));
-    }
-    __syncthreads();
-    double *ys = reinterpret_cast<double *>(sh + ((nf + 2 * a.Lout + 1) & ~1));   // [n][ch]
-    if (lane < 2) {
-        double c1[5], c2[5];
-#pragma unroll
-        for (int k = 0; k < 3; k++) { c1[k] = a.cd->kw1[k]; c2[k] = a.cd->kw2[k]; }
-        c1[3] = a.cd->kw1[4]; c1[4] = a.cd->kw1[5];
-        c2[3] = a.cd->kw2[4]; c2[4] = a.cd->kw2[5];
-        double v[4] = {0.0, 0.0, 0.0, 0.0};
-        int n = 0;
-        for (; n < len; n++)
-            ys[2 * n + ch] = hp_step(c2, v[2], v[3], bq_step(c1, v[0], v[1], (double)us[2 * n + ch]));
-        for (; n < a.Lout; n++) ys[2 * n + ch] = 0.0;
-        double *o = a.e + (j * 2 + ch) * AMX_KW_DIM;
-#pragma unroll
-        for (int d = 0; d < AMX_KW_DIM; d++) o[d] = v[d];
-        uint32_t *pq = a.pk + j * 4;
-        pq[ch] = __float_as_uint(pk);
-        pq[2 + ch] = (uint32_t)(px * 32768.0f);
-    }
-    __syncthreads();
-    const int64_t h0 = sg.tframe / a.hop;
-    const int split = (int)((h0 + 1) * a.hop - sg.tframe);
-    double acc[2][2][5] = {};                                     // [ch][piece][term]
-    for (int n = lane; n < len; n += 64) {
-        const double *r = a.G + (int64_t)n * AMX_KW_DIM;
-        const int pc = n < split ? 0 : 1;
-#pragma unroll
-        for (int cc = 0; cc < 2; cc++) {
-            const double y = ys[2 * n + cc];
-#pragma unroll
-            for (int p = 0; p < 2; p++) {
-                const double yy = p == pc ? y : 0.0;
-                acc[cc][p][0] = fma(yy, yy, acc[cc][p][0]);
-#pragma unroll
-                for (int d = 0; d < 4; d++) acc[cc][p][1 + d] = fma(yy, r[d], acc[cc][p][1 + d]);
-            }
-        }
-    }
-#pragma unroll
-    for (int cc = 0; cc < 2; cc++)
-#pragma unroll
-        for (int p = 0; p < 2; p++)
-#pragma unroll
-            for (int k = 0; k < 5; k++) {
-                double x = acc[cc][p][k];
-#pragma unroll
-                for (int o = 1; o < 64; o <<= 1) x += __shfl_xor(x, o);
-                acc[cc][p][k] = x;
-            }
-    if (lane < 2) {
-        double *te = a.eterms + (j * 2 + ch) * 10;
-#pragma unroll
-        for (int p = 0; p < 2; p++)
-#pragma unroll
-            for (int k = 0; k < 5; k++) te[p * 5 + k] = ch ? acc[1][p][k] : acc[0][p][k];
-    }
+    double acc[2][2][5] = {};
+    for (int n = lane; n < s.len; n += 64) up_terms_add(acc, n, (int)s.split, ys + 2 * n, a.G);
+    up_terms_reduce_store(a, j, ch, acc);
 }
 
 // hop pieces' energies from the exact start states: E = sum yz^2 + 2 s.q + s^T Q s,
@@ -739,10 +561,8 @@ __global__ void __launch_bounds__(AMX_BLOCK) k_up_energy(UpArgs a) {
     if (i >= 2 * (int64_t)a.n_kseg) return;
     const int64_t j = i >> 1;
     const int ch = (int)(i & 1);
-    const KwSegDev sg = a.ks[j];
-    const int64_t h0 = sg.tframe / a.hop;
-    const int split = (int)((h0 + 1) * a.hop - sg.tframe);
-    const int len = sg.len;
+    const UpSeg seg = up_seg(a, j);
+    const int split = (int)seg.split, len = seg.len;
     const double *s = a.s + (j * 2 + ch) * AMX_KW_DIM;
     const double *t = a.eterms + (j * 2 + ch) * 10;
     double sv[4];
@@ -776,13 +596,17 @@ __global__ void __launch_bounds__(AMX_BLOCK) k_up_energy(UpArgs a) {
     double *o = a.parts + j * 4;
     o[ch] = E0;
     o[2 + ch] = E1;
-    if (ch == 0) a.part_hop[j] = h0;
+    if (ch == 0) a.part_hop[j] = seg.sg.tframe / a.hop;
 }
 
 hipError_t launch_up1(const UpArgs &a, hipStream_t st, hipStream_t aux, hipEvent_t fork, hipEvent_t join) {
     if (a.n_kseg <= 0) return hipSuccess;
     const unsigned nblk = (unsigned)((a.n_kseg + AMX_UP_BLOCK / 2 - 1) / (AMX_UP_BLOCK / 2));
-    if (a.static_l > 0 && !a.lin && a.Lin + UP_TAPS <= AMX_UPE_NF && a.n_slow < (1 << 20)) {
+    // one wave's LDS: the staged frames, the 2 x Lout resampled samples, the K filter's outputs
+    auto wave_lds = [&](int row) {
+        return (((size_t)a.Lin + row + 2 * (size_t)a.Lout + 1) & ~(size_t)1) * 4 + (size_t)a.Lout * 16;
+    };
+    if (a.static_l > 0 && a.Lin + SWR_TAPS <= AMX_UPE_NF && a.n_slow < (1 << 20)) {
         // the left-over segments are k_up's first workgroups (dispatched first, so their
         // serial K filter overlaps the fast segments): no second stream, no join
         const unsigned ne = (unsigned)a.n_slow;
@@ -803,9 +627,7 @@ hipError_t launch_up1(const UpArgs &a, hipStream_t st, hipStream_t aux, hipEvent
                 if (e == hipSuccess) e = hipStreamWaitEvent(aux, fork, 0);
                 if (e != hipSuccess) return e;
             }
-            hipLaunchKernelGGL(k_up_edge, dim3((unsigned)a.n_slow), dim3(64),
-                               (size_t)((a.Lin + UP_TAPS + 2 * a.Lout + 1) & ~1) * 4 + (size_t)a.Lout * 16,
-                               es, a);
+            hipLaunchKernelGGL(k_up_wave<false>, dim3((unsigned)a.n_slow), dim3(64), wave_lds(SWR_TAPS), es, a);
             if (side) {
                 hipError_t e = hipEventRecord(join, aux);
                 if (e != hipSuccess) return e;
@@ -826,10 +648,8 @@ hipError_t launch_up1(const UpArgs &a, hipStream_t st, hipStream_t aux, hipEvent
             hipError_t e = hipStreamWaitEvent(st, join, 0);
             if (e != hipSuccess) return e;
         }
-    } else if (a.taps != UP_TAPS) {
-        const size_t nf = (size_t)a.Lin + a.alloc;
-        hipLaunchKernelGGL(k_up_wide, dim3((unsigned)a.n_slow), dim3(64),
-                           ((nf + 2 * (size_t)a.Lout + 1) & ~(size_t)1) * 4 + (size_t)a.Lout * 16, st, a);
+    } else if (a.taps != SWR_TAPS) {
+        hipLaunchKernelGGL(k_up_wave<true>, dim3((unsigned)a.n_slow), dim3(64), wave_lds(a.alloc), st, a);
     } else {
         hipLaunchKernelGGL(k_up_slow, dim3((unsigned)((a.n_slow + AMX_UP_BLOCK / 2 - 1) / (AMX_UP_BLOCK / 2))),
                            dim3(AMX_UP_BLOCK), 0, st, a);

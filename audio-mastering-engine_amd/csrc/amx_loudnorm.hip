@@ -12,61 +12,16 @@
 //     form for the tracks that one does not take.
 // Floating point: no FMA contraction (the reference's C is compiled that way too,
 // -ffp-contract=off in the oracle), so every expression keeps its operation order.
-#include "amx_dev.hpp"
+#include "amx_swr_dev.hpp"  // the resampler arithmetic (shared with amx_loud192.hip, amx_resample.hip)
 #include "amx_ln_dev.hpp"    // the frame geometry, block helpers and r128_in statistics (shared with k_ln_dyn)
 
 #pragma clang fp contract(off)
 
 namespace amx {
 
-#define LN_TAPS 32
-#define LN_C 15
-
-// --------------------------------------------------------------- resampler
-__device__ __forceinline__ int64_t ln_reflect(int64_t k, int64_t n) {
-    for (int it = 0; it < 64; it++) {
-        if (k < 0) k = -k;
-        else if (k >= n) k = 2 * n - 1 - k;
-        else return k;
-    }
-    return 0;
-}
-
-__device__ __forceinline__ float ln_dot(const float *w, const float *__restrict__ h) {
-    float a[8];
-#pragma unroll
-    for (int k = 0; k < 8; k++) {
-        float acc = __builtin_fmaf(w[k], h[k], 0.0f);
-        acc = __builtin_fmaf(w[k + 8], h[k + 8], acc);
-        acc = __builtin_fmaf(w[k + 16], h[k + 16], acc);
-        acc = __builtin_fmaf(w[k + 24], h[k + 24], acc);
-        a[k] = acc;
-    }
-    const float b0 = a[0] + a[4], b1 = a[1] + a[5], b2 = a[2] + a[6], b3 = a[3] + a[7];
-    return (b0 + b2) + (b1 + b3);
-}
-
-typedef float ln_f2 __attribute__((ext_vector_type(2)));
 typedef unsigned lp_u4 __attribute__((ext_vector_type(4)));
 
-// ln_dot with the 8 chains as 4 packed pairs (v_pk_fma_f32 / v_pk_add_f32): the same
-// operations lane by lane, the first term a fused multiply-add onto 0 as in ln_dot
-template <class P>
-__device__ __forceinline__ float ln_dot2(const float *w, P h) {
-    ln_f2 acc4[4];
-#pragma unroll
-    for (int k = 0; k < 8; k += 2) {
-        ln_f2 acc = __builtin_elementwise_fma(ln_f2{w[k], w[k + 1]}, ln_f2{h[k], h[k + 1]}, ln_f2{0.0f, 0.0f});
-        acc = __builtin_elementwise_fma(ln_f2{w[k + 8], w[k + 9]}, ln_f2{h[k + 8], h[k + 9]}, acc);
-        acc = __builtin_elementwise_fma(ln_f2{w[k + 16], w[k + 17]}, ln_f2{h[k + 16], h[k + 17]}, acc);
-        acc = __builtin_elementwise_fma(ln_f2{w[k + 24], w[k + 25]}, ln_f2{h[k + 24], h[k + 25]}, acc);
-        acc4[k >> 1] = acc;
-    }
-    const ln_f2 b01 = acc4[0] + acc4[2], b23 = acc4[1] + acc4[3];
-    const ln_f2 c = b01 + b23;
-    return c.x + c.y;
-}
-
+// --------------------------------------------------------------- resampler
 // The M == 1 rates (192 kHz / L: 48 kHz L = 4, 96 kHz 2, 64 kHz 3, 32 kHz 6, 192 kHz 1):
 // output j = frame j / L, phase j % L.  One thread per LN_UPF consecutive input frames:
 // one window of 31 + LN_UPF frames (loaded once: 35 loads for 4 frames instead of 128),
@@ -83,7 +38,7 @@ __global__ void __launch_bounds__(AMX_BLOCK) k_ln_up_static(const uint32_t *__re
                                                             const float *__restrict__ bank, int64_t j0, int64_t j1,
                                                             float *__restrict__ u, const int32_t *__restrict__ gate) {
     if (AMX_LN_GATED(gate)) return;
-    constexpr int NW = LN_TAPS + LN_UPF - 1;
+    constexpr int NW = SWR_TAPS + LN_UPF - 1;
     constexpr bool STAGE = L % 2 == 0;
     constexpr int TF = 2 * L * LN_UPF;                 // floats a thread produces
     __shared__ __attribute__((aligned(16))) float s_o[STAGE ? AMX_BLOCK * TF : 4];
@@ -97,8 +52,8 @@ __global__ void __launch_bounds__(AMX_BLOCK) k_ln_up_static(const uint32_t *__re
         const bool act = bi < nblk;
         const int64_t fb = f0 + (act ? bi : b0) * LN_UPF;   // this thread's first frame
         float w0[NW], w1[NW];
-        const int64_t g = fb - LN_C;
-        static_assert(LN_UPF == 4 && LN_C % 4 == 3, "the 16-B window loads start one frame early");
+        const int64_t g = fb - SWR_C;
+        static_assert(LN_UPF == 4 && SWR_C % 4 == 3, "the 16-B window loads start one frame early");
         if (g >= 1 && g - 1 + NW + 1 <= n_in && ((reinterpret_cast<uintptr_t>(x + g - 1) & 15) == 0)) {
             // 16-B loads of frames g - 1 .. g + NW - 1 (g - 1 = fb - 16: 16-B aligned when x is)
             uint32_t wv[NW + 1];
@@ -109,22 +64,22 @@ __global__ void __launch_bounds__(AMX_BLOCK) k_ln_up_static(const uint32_t *__re
             }
 #pragma unroll
             for (int i = 0; i < NW; i++) {
-                w0[i] = (float)lo16(wv[i + 1]) * (1.0f / 32768.0f);
-                w1[i] = (float)hi16(wv[i + 1]) * (1.0f / 32768.0f);
+                w0[i] = swr_tap(wv[i + 1], 0);
+                w1[i] = swr_tap(wv[i + 1], 1);
             }
         } else if (g >= 0 && g + NW <= n_in) {
 #pragma unroll
             for (int i = 0; i < NW; i++) {
                 const uint32_t v = x[g + i];
-                w0[i] = (float)lo16(v) * (1.0f / 32768.0f);
-                w1[i] = (float)hi16(v) * (1.0f / 32768.0f);
+                w0[i] = swr_tap(v, 0);
+                w1[i] = swr_tap(v, 1);
             }
         } else {
 #pragma unroll
             for (int i = 0; i < NW; i++) {
-                const uint32_t v = x[ln_reflect(g + i, n_in)];
-                w0[i] = (float)lo16(v) * (1.0f / 32768.0f);
-                w1[i] = (float)hi16(v) * (1.0f / 32768.0f);
+                const uint32_t v = x[swr_reflect(g + i, n_in)];
+                w0[i] = swr_tap(v, 0);
+                w1[i] = swr_tap(v, 1);
             }
         }
         // the whole workgroup's outputs in range: frames f0 + 4 b0 .. + 4 * AMX_BLOCK
@@ -143,11 +98,11 @@ __global__ void __launch_bounds__(AMX_BLOCK) k_ln_up_static(const uint32_t *__re
             float o[2 * L];
 #pragma unroll
             for (int ph = 0; ph < L; ph++) {
-                uint64_t bp = reinterpret_cast<uint64_t>(bank + ph * LN_TAPS);
+                uint64_t bp = reinterpret_cast<uint64_t>(bank + ph * SWR_TAPS);
                 asm volatile("" : "+s"(bp) : "v"(dep));
                 const ConstF h = (ConstF)bp;
-                o[2 * ph] = ln_dot2(w0 + k, h);
-                o[2 * ph + 1] = ln_dot2(w1 + k, h);
+                o[2 * ph] = swr_dot32_pk(w0 + k, h);
+                o[2 * ph + 1] = swr_dot32_pk(w1 + k, h);
                 dep = o[2 * ph + 1];
             }
             if constexpr (STAGE) {
@@ -207,21 +162,21 @@ __global__ void __launch_bounds__(AMX_BLOCK) k_ln_upsample(const uint32_t *__res
         const int64_t pos = j * r.dst, idx = pos / r.src;
         const int64_t base = idx / r.pc;
         const int ph = (int)(idx % r.pc);
-        float w0[LN_TAPS], w1[LN_TAPS];
+        float w0[SWR_TAPS], w1[SWR_TAPS];
 #pragma unroll
-        for (int i = 0; i < LN_TAPS; i++) {
-            const uint32_t v = x[ln_reflect(base - LN_C + i, n_in)];
-            w0[i] = (float)lo16(v) * (1.0f / 32768.0f);
-            w1[i] = (float)hi16(v) * (1.0f / 32768.0f);
+        for (int i = 0; i < SWR_TAPS; i++) {
+            const uint32_t v = x[swr_reflect(base - SWR_C + i, n_in)];
+            w0[i] = swr_tap(v, 0);
+            w1[i] = swr_tap(v, 1);
         }
-        const float *h = r.bank + (int64_t)ph * LN_TAPS;
+        const float *h = r.bank + (int64_t)ph * SWR_TAPS;
         if (r.lin) {
             const float wf = (float)(pos - idx * r.src) * (1.0f / (float)r.src);
-            u[2 * j] = swr_dot_lin(w0, h, h + LN_TAPS, wf);
-            u[2 * j + 1] = swr_dot_lin(w1, h, h + LN_TAPS, wf);
+            u[2 * j] = swr_dot_lin(w0, h, h + SWR_TAPS, wf);
+            u[2 * j + 1] = swr_dot_lin(w1, h, h + SWR_TAPS, wf);
         } else {
-            u[2 * j] = ln_dot(w0, h);
-            u[2 * j + 1] = ln_dot(w1, h);
+            u[2 * j] = swr_dot32(w0, h);
+            u[2 * j + 1] = swr_dot32(w1, h);
         }
     }
 }
@@ -239,26 +194,14 @@ __global__ void __launch_bounds__(AMX_BLOCK) k_ln_upsample_wide(const uint32_t *
         const int64_t pos = j * r.dst, idx = pos / r.src;
         const int64_t base = idx / r.pc;
         const int ph = (int)(idx % r.pc);
-        const float *h = r.bank + (int64_t)ph * r.alloc;
-        float a0[8], a1[8];
-#pragma unroll
-        for (int k = 0; k < 8; k++) {
-            const uint32_t v = x[ln_reflect(base - c + k, n_in)];
-            a0[k] = __builtin_fmaf((float)lo16(v) * (1.0f / 32768.0f), h[k], 0.0f);
-            a1[k] = __builtin_fmaf((float)hi16(v) * (1.0f / 32768.0f), h[k], 0.0f);
-        }
-        for (int q = 8; q < r.alloc; q += 8) {
-#pragma unroll
-            for (int k = 0; k < 8; k++) {
-                const uint32_t v = x[ln_reflect(base - c + q + k, n_in)];
-                a0[k] = __builtin_fmaf((float)lo16(v) * (1.0f / 32768.0f), h[q + k], a0[k]);
-                a1[k] = __builtin_fmaf((float)hi16(v) * (1.0f / 32768.0f), h[q + k], a1[k]);
-            }
-        }
-        const float b0 = a0[0] + a0[4], b1 = a0[1] + a0[5], b2 = a0[2] + a0[6], b3 = a0[3] + a0[7];
-        const float e0 = a1[0] + a1[4], e1 = a1[1] + a1[5], e2 = a1[2] + a1[6], e3 = a1[3] + a1[7];
-        u[2 * j] = (b0 + b2) + (b1 + b3);
-        u[2 * j + 1] = (e0 + e2) + (e1 + e3);
+        const swr_f2 o = swr_dot_rows<swr_f2>(
+            [&](int k) {
+                const uint32_t v = x[swr_reflect(base - c + k, n_in)];
+                return swr_f2{swr_tap(v, 0), swr_tap(v, 1)};
+            },
+            r.bank + (int64_t)ph * r.alloc, 1, r.alloc);
+        u[2 * j] = o.x;
+        u[2 * j + 1] = o.y;
     }
 }
 
@@ -1528,7 +1471,7 @@ static void ln_upsample(const uint32_t *x, int64_t n_in, const SwrDev &r, int64_
         const int64_t nb = (n + AMX_BLOCK - 1) / AMX_BLOCK;
         return dim3((unsigned)(nb < 8192 ? nb : 8192));
     };
-    if (r.taps != LN_TAPS) {
+    if (r.taps != SWR_TAPS) {
         hipLaunchKernelGGL(k_ln_upsample_wide, grid(j1 - j0), dim3(AMX_BLOCK), 0, st, x, n_in, r, j0, j1, u, gate);
         return;
     }

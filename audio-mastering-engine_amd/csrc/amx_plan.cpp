@@ -371,6 +371,10 @@ amx::UpArgs up_args(const amx_plan *p, const int16_t *d_out, const int16_t *d_ed
     a.pk = wsp<uint32_t>(d_ws, p->o_pk);
     return a;
 }
+// the plan's resampler to 192 kHz as loudnorm's upsamplers take it
+amx::SwrDev swr_dev(const amx_plan *p) {
+    return amx::SwrDev{p->up_pc, p->up_lin, p->up_src, p->up_dst, p->d_bank, p->up_taps, p->up_alloc};
+}
 // ---- loudnorm's 192 kHz modes: scratch layout (amx_loudnorm.hip)
 #define LN_FIRST_FRAMES 576000     // frame_size(192000, 3000)
 struct LnLayout {
@@ -652,7 +656,7 @@ int amx_loudnorm_192k_ex(amx_plan *p, int32_t track, const amx_loudnorm_desc *d,
                          d_summary, d_ws2, a, q, n192))
         return rc;
     const SpanDev &sp = p->spans[track];
-    amx::SwrDev r{p->up_pc, p->up_lin, p->up_src, p->up_dst, p->d_bank, p->up_taps, p->up_alloc};
+    const amx::SwrDev r = swr_dev(p);
     HIPCHK(amx::launch_loudnorm(a, q, reinterpret_cast<const uint32_t *>(d_out) + sp.out_off, sp.out_n, r,
                                 d->reuse_stream == 0, (hipStream_t)stream));
     return AMX_OK;
@@ -690,7 +694,7 @@ int amx_loudnorm_192k_shard(amx_plan *p, int32_t track, const amx_loudnorm_desc 
     q.rec_in = sh->kb > 0 ? sh->d_rec_in : nullptr;
     q.rec_out = sh->ke < q.K ? sh->d_rec_out : nullptr;
     const SpanDev &sp = p->spans[track];
-    amx::SwrDev r{p->up_pc, p->up_lin, p->up_src, p->up_dst, p->d_bank, p->up_taps, p->up_alloc};
+    const amx::SwrDev r = swr_dev(p);
     // the positions segments [kb, ke) emit
     const LnLayout lo = ln_layout(n192);
     const int64_t y_lo = ln_seg_base(lo, n192, sh->kb), y_hi = sh->ke < lo.K ? ln_seg_base(lo, n192, sh->ke) : n192;
@@ -1387,7 +1391,7 @@ int amx_mc_loudnorm_192k(amx_plan *p, int32_t channels, const amx_loudnorm_desc 
     hipStream_t st = (hipStream_t)stream;
     if (d->reuse_stream == 0) {
         // each channel pair through the stereo upsampler into its plane
-        amx::SwrDev r{p->up_pc, p->up_lin, p->up_src, p->up_dst, p->d_bank, p->up_taps, p->up_alloc};
+        const amx::SwrDev r = swr_dev(p);
         for (int t = 0; t < P; t++) {
             const SpanDev &sp = p->spans[t];
             HIPCHK(amx::launch_ln_upsample(reinterpret_cast<const uint32_t *>(d_pairs) + sp.out_off, sp.out_n, r, 0,

@@ -13,7 +13,7 @@ struct amx_plan : amx::PlanHost {
     std::vector<void *> owned;
     const int32_t *gate = nullptr;   // amx_plan_set_gate: the per-sample kernels' mode word
     int32_t *publish = nullptr;      // amx_plan_set_publish: pinned host words k_decide also stores
-    hipStream_t up_aux = nullptr;            // k_up_edge's stream, forked from / joined to the caller's
+    hipStream_t up_aux = nullptr;            // k_up_wave<false>'s stream, forked from / joined to the caller's
     hipEvent_t up_fork = nullptr, up_join = nullptr;
     int kw_rest_states = 0;  // the last amx_loudness_pass1 left the K-filter start states from rest
     int kw_eb_ready = 0;     // the K scan's block sums (o_ebk) are those of the current e
@@ -35,7 +35,7 @@ struct amx_plan : amx::PlanHost {
     double *d_tailpow = nullptr;
     int32_t *d_obase = nullptr, *d_oph = nullptr;
     float *d_owt = nullptr;
-    int32_t *d_slow = nullptr;   // K segments k_up_edge takes (static / poly path); n_slow of them
+    int32_t *d_slow = nullptr;   // K segments k_up_wave<false> takes (static / poly path); n_slow of them
     int32_t *d_fcnt = nullptr;   // k_up_poly: outputs per segment frame
     float *d_bankn = nullptr;    // k_up_poly: bank rows in output order
     float *d_bank = nullptr;

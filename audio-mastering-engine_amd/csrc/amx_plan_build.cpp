@@ -144,7 +144,7 @@ int Lti::window_powers(int64_t LS, double tol, int max_k, std::vector<double> &o
 // (float32 bank, scale 1).  Upsampling only (factor 1); L / M = out / in reduced (output j
 // sits at input position j M / L).  The bank has L phases when L <= 1024 (exact_rational)
 // and 1024 otherwise (22.05 / 11.025 kHz): the position then falls between two phases and
-// libswresample's linear kernel interpolates (amx_dev.hpp swr_dot_lin).
+// libswresample's linear kernel interpolates (amx_swr_dev.hpp swr_dot_lin).
 int swr_geometry(int in_rate, int out_rate, int *L, int *M) {
     if (in_rate <= 0 || out_rate <= 0) return -1;
     int64_t a = in_rate, b = out_rate;

@@ -87,7 +87,7 @@ struct PlanHost {
     int up_taps = 32, up_alloc = 32;   // filter_length / filter_alloc (> 32: downsampling)
     int64_t up_src = 1, up_dst = 1;
     int up_poly = 0;             // k_up_poly's form (AMX_UP_POLY) when the rate has one
-    int64_t n_slow = 0;          // K segments k_up_edge takes (static / poly path): slow
+    int64_t n_slow = 0;          // K segments k_up_wave<false> takes (static / poly path): slow
     double kdf_b[5] = {0, 0, 0, 0, 0}, kdf_a[5] = {0, 0, 0, 0, 0};   // K filter, fused direct form (192 kHz)
     int mask = 0, D = 0;
     int lev_eq = 0, lev_x = 0, lev_kw = 0;

@@ -26,7 +26,7 @@
 // kHz, which needs the dynamic-LDS attribute), else from global memory (k_resample<false>:
 // 2.3 to 2.7 times slower where both run).  Every output sample is written
 // by exactly one store and nothing else is written.
-#include "amx_dev.hpp"
+#include "amx_swr_dev.hpp"
 
 namespace amx {
 
@@ -43,14 +43,6 @@ static int rs_window(int L, int M, int alloc) {
 }
 static int rs_pitch(int window) { return ((window - 2 + 31) / 32) * 32 + 2; }
 
-__device__ __forceinline__ int64_t rs_reflect(int64_t k, int64_t n) {
-    for (;;) {
-        if (k < 0) k = -k;
-        else if (k >= n) k = 2 * n - 1 - k;
-        else return k;
-    }
-}
-
 // One tile: `tile` output frames from j0, by the 256 threads `tid` of one tile group.
 // win: the group's window planes; bank: ONE: the row; else tap-major [alloc][L], in global
 // memory or (k_resample_lb) in LDS.  The caller puts a barrier between the two halves.
@@ -64,8 +56,7 @@ __device__ __forceinline__ void rs_stage(float *win, const int16_t *__restrict__
     const int wn = (r0 + (tile - 1) * g.M) / g.L + g.alloc;
     for (int e = tid; e < wn * g.C; e += AMX_BLOCK) {
         const int x = e / g.C, c = e - x * g.C;
-        const int64_t k = rs_reflect(w0 + x, n);
-        win[c * g.pitch + x] = (float)in[k * g.C + c] * (1.0f / 32768.0f);
+        win[c * g.pitch + x] = swr_s16(in[swr_reflect(w0 + x, n) * g.C + c]);
     }
 }
 
@@ -77,17 +68,9 @@ __device__ __forceinline__ void rs_dots(const float *win, const float *__restric
         const int t = r0 + f * g.M;
         const int xb = t / g.L, ph = t - xb * g.L;
         const float *w = win + c * g.pitch + xb;
-        const float *h = ONE ? bank : bank + ph;
-        const int hs = ONE ? 1 : g.L;                  // tap stride of the bank
-        float a[8];
-#pragma unroll
-        for (int k = 0; k < 8; k++) a[k] = 0.0f;
-        for (int q = 0; q < g.alloc; q += 8) {
-#pragma unroll
-            for (int k = 0; k < 8; k++) a[k] = __builtin_fmaf(w[q + k], h[(q + k) * hs], a[k]);
-        }
-        const float b0s = a[0] + a[4], b1s = a[1] + a[5], b2s = a[2] + a[6], b3s = a[3] + a[7];
-        out[j0 * g.C + s] = q_f32_to_s16_ffmpeg((b0s + b2s) + (b1s + b3s));
+        // the bank's tap stride: ONE: the row; else tap-major, row ph
+        const float v = swr_dot_rows<float>([&](int k) { return w[k]; }, ONE ? bank : bank + ph, ONE ? 1 : g.L, g.alloc);
+        out[j0 * g.C + s] = q_f32_to_s16_ffmpeg(v);
     }
 }
 

@@ -392,7 +392,7 @@ AMX_API int amx_plan_set_gate(amx_plan *plan, const int32_t *d_gate);
 AMX_API int amx_loudness_pass1(amx_plan *plan, const int16_t *d_out, const int16_t *d_edge,
                                double *d_kw_tail, double *d_peak, void *d_ws, void *stream);
 /* amx_loudness_pass1 in its two launches (same arguments): part 0 = the one pass over
- * the samples (at 192 kHz: k_up, and k_up_edge beside it on the plan's second stream),
+ * the samples (at 192 kHz: k_up, and k_up_wave<false> beside it on the plan's second stream),
  * part 1 = peaks, scan, tails.  pass1 == part 0 then part 1; split so a caller can
  * time the sample pass alone. */
 AMX_API int amx_loudness_pass1_part(amx_plan *plan, int32_t part, const int16_t *d_out,

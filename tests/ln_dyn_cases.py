@@ -69,11 +69,12 @@ def _measured(capi, st, measured_i, thresh, offset):
                              thresh, offset)
 
 
-def _run_stereo(name):
+def _run_stereo(name, signal=None):
+    """signal: (float32 [n, 2], rate) in place of the named case's (tests/up192_cases.py)"""
     import torch
     from amx import capi
     from amx.engine import MasteringJob
-    x, fs = _stereo_signal(name)
+    x, fs = signal if signal is not None else _stereo_signal(name)
     x16 = quantize(x)
     n = x16.shape[0]
     env = {"AMX_LN_SEG": "4", "AMX_LN_WARM": "3"} if name == "handover" else {}

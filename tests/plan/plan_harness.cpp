@@ -607,6 +607,57 @@ void run_case(const Case &c) {
     }
 }
 
+// --plan NAME FS N0[,N1...] F0|- TOTAL|- KNOB=VALUE|-: a measure-only plan of tracks laid back to
+// back (F0 / TOTAL: the first track's place in its file), reported as a case, and its
+// resampler bank: every row (the pc phases and the interpolation partner) has a tap > 0
+void run_plan(char **a) {
+    Case c;
+    c.name = a[0];
+    c.d = desc_eq(atoi(a[1]));
+    c.d.measure_only = 1;
+    int64_t off = 0;
+    int32_t t = 0;
+    for (const char *s = a[2]; *s; t++) {
+        char *end;
+        amx_chunk k{};
+        k.track = t;
+        k.in_offset = off;
+        k.frames = strtoll(s, &end, 10);
+        off += k.frames;
+        c.ch.push_back(k);
+        s = *end ? end + 1 : end;
+    }
+    if (strcmp(a[3], "-")) c.f0.assign(c.ch.size(), 0), c.f0[0] = atoll(a[3]);
+    if (strcmp(a[4], "-")) {
+        for (const amx_chunk &k : c.ch) c.tot.push_back(k.frames);
+        c.tot[0] = atoll(a[4]);
+        if (c.f0.empty()) c.f0.assign(c.ch.size(), 0);
+    }
+    std::string knob = a[5];
+    const size_t eq_at = knob.find('=');
+    if (eq_at != std::string::npos) {
+        knob[eq_at] = 0;
+        c.env.push_back({knob.c_str(), knob.c_str() + eq_at + 1});
+    }
+    set_env(c);
+    printf("case %s\n", c.name.c_str());
+    amx_plan *p = nullptr;
+    const int rc = create(c, &p);
+    printf("rc=%d err=%s\n", rc, rc ? amx_last_error() : "");
+    if (rc == AMX_OK) {
+        report("", p);
+        const int n_rows = (int)(standin::size_of(p->d_bank) / sizeof(float) / (size_t)p->up_alloc);
+        int rows = 0, bad = 0;
+        if (p->resamp && p->up_ok)
+            for (; rows < n_rows; rows++) {
+                const float *h = p->d_bank + (size_t)rows * p->up_alloc;
+                bad += std::none_of(h, h + p->up_alloc, [](float v) { return v > 0.0f; }) ? 1 : 0;
+            }
+        printf("bank rows=%d without_positive_tap=%d\n", rows, bad);
+    }
+    amx_plan_free(p);
+}
+
 // ------------------------------------------------------------------ ownership
 #define OWN(c)                                                  \
     do {                                                        \
@@ -691,9 +742,18 @@ void ownership() {
 
 int main(int argc, char **argv) {
     const char *only = nullptr;
+    bool plans = false;
     for (int i = 1; i < argc; i++) {
         if (!strcmp(argv[i], "--full")) ph::g_full = true;
-        else only = argv[i];
+        else if (!strcmp(argv[i], "--plan") && i + 6 < argc) {
+            ph::run_plan(argv + i + 1);
+            i += 6;
+            plans = true;
+        } else only = argv[i];
+    }
+    if (plans) {
+        printf("%d failed\n", ph::g_bad);
+        return ph::g_bad ? 1 : 0;
     }
     for (const ph::Case &c : ph::cases())
         if (!only || c.name == only) ph::run_case(c);

@@ -36,9 +36,9 @@ pytestmark = pytest.mark.skipif(shutil.which("g++") is None, reason="no host C++
 
 
 @pytest.fixture(scope="module")
-def harness_output(tmp_path_factory):
+def harness_exe(tmp_path_factory):
     """the harness, built with the library's floating-point flags plus the sanitizers (the
-    kernel launchers stay unresolved: nothing launches), run once over all cases"""
+    kernel launchers stay unresolved: nothing launches)"""
     exe = str(tmp_path_factory.mktemp("plan") / "plan_harness")
     r = subprocess.run(["g++", "-std=c++17", "-ffp-contract=off", *SAN, "-D__HIP_PLATFORM_AMD__",
                         "-I" + ROCM_INC, "-I" + CSRC,
@@ -48,7 +48,13 @@ def harness_output(tmp_path_factory):
     if r.returncode != 0 and "asan" in r.stderr.lower() and "cannot find" in r.stderr.lower():
         pytest.skip("no sanitizer runtime for the host compiler: %s" % r.stderr[-300:])
     assert r.returncode == 0, r.stderr[-3000:]
-    r = subprocess.run([exe], capture_output=True, text=True, env=ENV, timeout=600)
+    return exe
+
+
+@pytest.fixture(scope="module")
+def harness_output(harness_exe):
+    """the harness run once over all cases"""
+    r = subprocess.run([harness_exe], capture_output=True, text=True, env=ENV, timeout=600)
     assert "ERROR: AddressSanitizer" not in r.stderr and "ERROR: LeakSanitizer" not in r.stderr and \
         "runtime error" not in r.stderr, r.stderr[-6000:]
     return r
@@ -124,3 +130,64 @@ def test_builder_compiles_without_hip(tmp_path):
     r = subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-c", os.path.join(CSRC, "amx_plan_build.cpp"),
                         "-o", str(tmp_path / "amx_plan_build.o")], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-3000:]
+
+
+@pytest.fixture(scope="module")
+def up192_plans(harness_exe):
+    """the plan of every measurement case of tests/up192_cases.py (the harness's --plan)"""
+    import up192_cases
+    args = []
+    for name, pl in up192_cases.PLANS.items():
+        args += ["--plan", name, str(pl["fs"]), ",".join(str(n) for n in pl["spans"]),
+                 str(pl["f0"][0]) if pl["f0"] else "-", str(pl["total"][0]) if pl["total"] else "-",
+                 ",".join("%s=%s" % kv for kv in pl["env"].items()) or "-"]
+    r = subprocess.run([harness_exe] + args, capture_output=True, text=True, env=ENV, timeout=600)
+    assert "ERROR: AddressSanitizer" not in r.stderr and "ERROR: LeakSanitizer" not in r.stderr and \
+        "runtime error" not in r.stderr, r.stderr[-6000:]
+    assert r.returncode == 0, r.stdout[-3000:]
+    return _cases(r.stdout)
+
+
+def _host(lines):
+    line = [ln for ln in lines if ln.startswith("host ")][0]
+    return dict(kv.split("=") for kv in line.split()[1:])
+
+
+def test_up192_cases_run_the_paths_they_are_there_for(up192_plans):
+    """tests/test_gpu_up192_digests.py's cases, rate for rate and length for length: the
+    unrolled k_up<L> with chunked left-overs, the five k_up_poly forms with left-overs on the
+    side stream, k_up_slow over every segment (with and without interpolation) and the wave
+    kernel over every segment of a downsampling rate; each with fast segments and left-overs
+    where the path has both"""
+    import up192_cases
+    assert sorted(k for k in up192_plans if k) == sorted(up192_cases.PLANS)
+    for name, pl in up192_cases.PLANS.items():
+        lines = up192_plans[name]
+        assert lines[0] == "rc=0 err=" and "inv ok" in lines, (name, lines[:1])
+        h = _host(lines)
+        print(name, {k: h[k] for k in ("up", "Lin", "Lout", "static", "lin", "taps", "poly", "nslow", "kseg")})
+        nslow, kseg = int(h["nslow"]), int(h["kseg"])
+        assert int(h["resamp"]) == 1 and int(h["ok"]) == 1, name
+        assert int(h["static"]) == pl["static_l"] and int(h["poly"]) == pl["poly"] and int(h["lin"]) == pl["lin"], (name, h)
+        assert (h["taps"] != "32/32") == pl["wide"], (name, h)
+        if pl["all_slow"]:
+            assert nslow == kseg and "int slow -" in lines, (name, h)
+        else:
+            # a span's first (mirrored or neighbour-fed) and last (partial) segments, the
+            # hop-split ones where the segment does not divide the hop; the rest fast
+            assert 2 * len(pl["spans"]) <= nslow < kseg - 3 and "int slow -" not in lines, (name, h)
+        if pl["static_l"]:
+            # (launch_up1: the left-overs are k_up's first workgroups while Lin + 32 <= 544)
+            assert int(h["Lin"]) + 32 <= 544, (name, h)
+
+
+def test_every_resampler_bank_row_has_a_positive_tap(up192_plans):
+    """the dot products' first term is a product, not fma(w, h, +0) (csrc/amx_swr_dev.hpp): the
+    two differ only when a whole row's products are zeros of negative sign, which the
+    positive main-lobe tap of every row rules out for inputs without a -0"""
+    for name, lines in up192_plans.items():
+        if name is None:
+            continue
+        bank = [ln for ln in lines if ln.startswith("bank ")]
+        assert len(bank) == 1 and bank[0].endswith(" without_positive_tap=0"), (name, bank)
+        assert int(bank[0].split()[1].split("=")[1]) >= 1, (name, bank)
