@@ -594,6 +594,18 @@ __device__ void limiter_block(const LimArgs &a, int bx, int nbx, double *lim_lds
     // 2. the last block of the track walks (one wave per block: its drain, then the count;
     // the walker acquires once before it reads the other blocks' records)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    // The walker rewrites the output (and trace) of every segment it re-runs: two workgroups
+    // plain-store the same bytes, ordered until now only by the relaxed count and the walker's
+    // acquire.  That is a race; a block that wrote output the walker may rewrite releases it
+    // before it counts.  (Observed: with several tracks in one launch a re-run segment kept
+    // its first output.  Supposed mechanism: the block's line, still dirty in its XCD's L2,
+    // written back after the walker's from another XCD's.)  The wait after the fence is
+    // written as asm on purpose: the compiler may drop the fence's own wait when it has just
+    // seen the counter drained, and the count must not overtake the write-back.
+    if (nseg > 1 && bx < nseg) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
     unsigned old = 0;
     if (lane == 0) old = __hip_atomic_fetch_add(a.cnt + t, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     old = __shfl(old, 0);
