@@ -57,16 +57,29 @@ def _parse(path):
         cid, size = data[pos:pos + 4], struct.unpack(">I", data[pos + 4:pos + 8])[0]
         body = data[pos + 8:pos + 8 + size]
         if cid == b"COMM":
-            ch, frames, bits = struct.unpack(">hIh", body[:8])
-            fs = _ext80(body[8:18])
-            comp = body[18:22] if aifc and len(body) >= 22 else b"NONE"
-            comm = (ch, frames, bits, fs, comp)
+            comm = _comm(body, aifc)
         elif cid == b"SSND":
             off = struct.unpack(">I", body[:4])[0]
             ssnd = body[8 + off:]
         pos += 8 + size + (size & 1)
     if comm is None or ssnd is None:
         raise ValueError("AIFF without COMM/SSND chunk: %s" % path)
+    info, code, frames = _format(comm, path)
+    n = min(frames, len(ssnd) // info.block_align)
+    return info, code, ssnd[:n * info.block_align]
+
+
+def _comm(body, aifc):
+    """a COMM chunk's fields: (channels, sample frames, bits, rate, compression type)"""
+    ch, frames, bits = struct.unpack(">hIh", body[:8])
+    fs = _ext80(body[8:18])
+    comp = body[18:22] if aifc and len(body) >= 22 else b"NONE"
+    return ch, frames, bits, fs, comp
+
+
+def _format(comm, path):
+    """(WavInfo, PCM code, sample frames) of _comm's fields; ValueError for a format that
+    is not read"""
     ch, frames, bits, fs, comp = comm
     if ch <= 0 or bits <= 0:
         raise ValueError("AIFF with %d channels / %d-bit samples: %s" % (ch, bits, path))
@@ -86,9 +99,7 @@ def _parse(path):
     if code is None:
         raise ValueError("unsupported AIFF-C compression %r / %d-bit samples" % (comp, bits))
     tag = 3 if code.startswith("f") else 1
-    info = WavInfo(int(round(fs)), ch, tag, 8 * nbytes)
-    n = min(frames, len(ssnd) // info.block_align)
-    return info, code, ssnd[:n * info.block_align]
+    return WavInfo(int(round(fs)), ch, tag, 8 * nbytes), code, frames
 
 
 def read_aiff_raw(path):

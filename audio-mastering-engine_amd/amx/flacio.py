@@ -49,9 +49,11 @@ def is_flac(path):
 _MAX_SAMPLES_PER_BYTE = 6144
 
 
-def decode_flac(data, threads=0, with_blocks=False):
+def decode_flac(data, threads=0, with_blocks=False, alloc=None):
     """(int32 array [frames, channels] left-justified to 32 bits, FlacInfo) of FLAC bytes;
-    with_blocks: also the FLAC frames' block sizes in stream order (the demuxer's packets)"""
+    with_blocks: also the FLAC frames' block sizes in stream order (the demuxer's packets);
+    alloc(frames, channels): the int32 array to decode into (amx.files: a view of pinned
+    staging memory), None: a new one"""
     # the decoder reads the caller's bytes in place (no copy): a numpy view of them
     raw = np.frombuffer(data, np.uint8)
     o = _skip_id3(raw[:10].tobytes())
@@ -70,7 +72,7 @@ def decode_flac(data, threads=0, with_blocks=False):
         rc = L.amx_flac_decode(buf, size, None, 0, ctypes.byref(n), int(threads), None, 0, None)
         if rc != capi.AMX_OK:
             raise capi.AmxError("corrupt FLAC stream (amx_flac_decode %d)" % rc)
-    out = np.empty((n.value, info.channels), np.int32)
+    out = np.empty((n.value, info.channels), np.int32) if alloc is None else alloc(n.value, info.channels)
     got = ctypes.c_int64(0)
     # frames of at least 16 samples (the format's minimum block size but the last)
     max_blocks = n.value // 16 + 2

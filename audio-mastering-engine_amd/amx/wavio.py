@@ -21,6 +21,17 @@ class WavInfo:
 PCM_CODE = {(1, 8): "u8", (1, 16): "s16", (1, 24): "s24", (1, 32): "s32", (3, 32): "f32", (3, 64): "f64"}
 
 
+def chain_kind(channels, code):
+    """(channels_in, input_s16) of the chain input a file's samples become, and whether the
+    file's own bytes are that input already (no amx_pcm_to_s16 run).  Host only."""
+    if code == "f32":
+        return channels, False, True
+    if channels > 2:
+        # 3..8 channels: s16 [frames][C] as the split writes them (no duplication, :190)
+        return channels, True, code == "s16"
+    return 2, True, code == "s16" and channels == 2
+
+
 def _parse(path):
     with open(path, "rb") as f:
         data = f.read()

@@ -24,6 +24,9 @@ Mirrors audio_mastering_engine.py's call surface for the hot path:
   on any error ``"Error: ..."``, ``progress(0, 1)``, ``art(None)``,
   ``tag("Processing failed.")`` exactly like :131-137.
 * ``EQ_PRESETS`` (:32-38).
+* ``master_files(jobs, ...)`` -- a list of ``master_audio`` settings dicts in one call: the
+  files are read ahead and written behind on threads and those that can share a plan run
+  as one batch (amx/files.py); every output file is ``master_audio``'s.
 
 All per-sample work runs on the GPU (libamx.so via amx.engine): the host parses the
 WAV container and moves the file's own bytes to the device; the s16 conversion of
@@ -47,7 +50,7 @@ from amx.chunking import bounds_for  # noqa: E402
 from amx.settings import EQ_PRESETS, flac_decode_mode, multichannel_dynamic, output_rate  # noqa: E402,F401
 
 __all__ = ["master_audio", "process_audio", "process_audio_with_ffmpeg_pipeline", "EQ_PRESETS",
-           "master_array", "export_to_mp3"]
+           "master_array", "export_to_mp3", "master_files"]
 
 
 def _noop(*a, **k):
@@ -75,7 +78,7 @@ def _device_input(path, settings=None, on_info=None):
     settings key flac_decode = "device" a FLAC file's samples never exist on the host:
     amx_pcm_to_s16 reads the device decoder's array."""
     import torch
-    from amx import capi, flacio
+    from amx import flacio
     if flac_decode_mode(settings) == "device" and flacio.is_flac(path):
         d_raw, info, code = _flac_on_device(path)
         frames = int(d_raw.shape[0])
@@ -89,24 +92,24 @@ def _device_input(path, settings=None, on_info=None):
         on_info(info.sample_rate, info.channels)
     if d_raw is None:
         d_raw = torch.from_numpy(raw.copy()).to("cuda")
-    if code == "f32":
-        return d_raw.view(torch.float32), info.sample_rate, frames, info.channels, False, info
-    if info.channels > 2:
-        # 3..8 channels: s16 [frames][C] as the split writes them (no duplication, :190)
-        if code == "s16":
-            return d_raw.view(torch.int16), info.sample_rate, frames, info.channels, True, info
-        d_in = torch.empty((max(1, frames), info.channels), dtype=torch.int16, device="cuda")
-        capi.check(capi.load().amx_pcm_to_s16(capi.ptr(d_raw), frames, info.channels,
-                                              capi.PCM_FORMATS[code], capi.ptr(d_in),
-                                              capi.ptr_stream()), "amx_pcm_to_s16")
-        return d_in, info.sample_rate, frames, info.channels, True, info
-    if code == "s16" and info.channels == 2:
-        return d_raw.view(torch.int16), info.sample_rate, frames, 2, True, info
-    d_in = torch.empty((max(1, frames), 2), dtype=torch.int16, device="cuda")
-    capi.check(capi.load().amx_pcm_to_s16(capi.ptr(d_raw), frames, info.channels,
+    d_in, ch_in, s16 = _chain_input(d_raw, info.channels, code, frames)
+    return d_in, info.sample_rate, frames, ch_in, s16, info
+
+
+def _chain_input(d_raw, channels, code, frames, out=None):
+    """The file's samples on the device (d_raw: its bytes, or the device FLAC decoder's
+    array) as the chain input: (d_in, channels_in, input_s16).  out: an int16 device tensor
+    [frames, channels_in] that amx_pcm_to_s16 writes into when it runs (None: a new one)."""
+    import torch
+    from amx import capi
+    ch_in, s16, direct = wavio.chain_kind(channels, code)
+    if direct:
+        return d_raw.view(torch.int16 if s16 else torch.float32), ch_in, s16
+    d_in = out if out is not None else torch.empty((max(1, frames), ch_in), dtype=torch.int16, device="cuda")
+    capi.check(capi.load().amx_pcm_to_s16(capi.ptr(d_raw), frames, channels,
                                           capi.PCM_FORMATS[code], capi.ptr(d_in),
                                           capi.ptr_stream()), "amx_pcm_to_s16")
-    return d_in, info.sample_rate, frames, 2, True, info
+    return d_in, ch_in, s16
 
 
 def _write_output(path, y_device, fs, settings=None):
@@ -154,19 +157,22 @@ def _normalize_multichannel(job):
     return None
 
 
-def master_audio(settings, status_callback=None, progress_callback=None):
-    import torch
-    from amx.engine import MasteringJob
-
-    status = status_callback or _noop
-    progress = progress_callback or _noop
-    input_file, output_file = settings.get("input_file"), settings.get("output_file")
-    if not input_file or not output_file:
+def _check_settings(settings):
+    """what master_audio refuses before any file is read"""
+    if not settings.get("input_file") or not settings.get("output_file"):
         raise ValueError("Input or output file not specified.")              # :173
     flac_decode_mode(settings)                         # a bad flac_decode: before any file is read
     output_rate(settings, 0)                           # a bad output_rate likewise
     multichannel_dynamic(settings)                     # and a bad multichannel_dynamic
-    from amx.engine import delivery_rate, deliver
+
+
+def master_audio(settings, status_callback=None, progress_callback=None):
+    from amx.engine import delivery_rate
+
+    status = status_callback or _noop
+    progress = progress_callback or _noop
+    _check_settings(settings)
+    input_file, output_file = settings["input_file"], settings["output_file"]
     # a master rate the resampler cannot take to output_rate: before any kernel runs
     check = lambda rate, channels: delivery_rate(settings, rate, channels)   # noqa: E731
     status("Splitting audio into manageable chunks...")                       # :176
@@ -175,11 +181,24 @@ def master_audio(settings, status_callback=None, progress_callback=None):
     target = output_rate(settings, fs)
     bounds = bounds_for(frames, fs, info)                                     # :178
     status("Splitting complete.")                                             # :180
+    return _master_device(settings, status, progress, d_in, fs, frames, ch_in, s16, bounds, output_file, target)
+
+
+def _master_device(settings, status, progress, d_in, fs, frames, ch_in, s16, bounds, output_file, target,
+                   write=None, result=None):
+    """master_audio from "Splitting complete." on: the input is on the device (d_in, as
+    _device_input returns it) and split at `bounds`.  write(path, y_device, fs, settings):
+    what takes the finished master (None: _write_output); result: a dict that receives
+    mode, stats (the pass-1 strings or None) and sample_rate (as delivered) -- master_files
+    (amx.files) runs a file that is alone in its group through this very sequence."""
+    import torch
+    from amx.engine import MasteringJob, deliver
+    write = write or _write_output
     num_chunks = len(bounds)
     total_steps = num_chunks + 4                                              # :184
     if ch_in > 2:
         return _master_multichannel(settings, status, progress, d_in, fs, frames, ch_in, s16, bounds,
-                                    output_file, target)
+                                    output_file, target, write, result)
     job = MasteringJob(fs, ch_in, settings, [frames], input_s16=s16,
                        chunks=[(0, s, n) for s, n in bounds])
     # every chunk's chain runs in the same launches (chunks are independent,
@@ -198,11 +217,13 @@ def master_audio(settings, status_callback=None, progress_callback=None):
     # half of loudnorm's 192 kHz measurement)
     job.loudness_pass1()
     dyn = None
+    report = {}
     if settings.get("lufs") is not None:                                      # :216
         status("Normalizing final loudness...")                               # :217
         progress(num_chunks + 2, total_steps)                                 # :218
         try:
             dyn = _normalize(job)
+            report = job.report
         except Exception as e:                                                # :243-246
             # the reference logs any normalisation error and carries on with a copy of
             # the unnormalised track: here the track is finalised without the gain
@@ -224,14 +245,24 @@ def master_audio(settings, status_callback=None, progress_callback=None):
         y, out_fs = dyn[0], dyn[1]["sample_rate"]
     rate = {"sample_rate": out_fs}
     y = deliver(y, rate, target)                       # output_rate: the resampler after the alimiter
-    _write_output(output_file, y, rate["sample_rate"], settings)
+    _fill_result(result, report, rate)
+    write(output_file, y, rate["sample_rate"], settings)
     progress(total_steps, total_steps)                                        # :224
     logging.info(f"Finished GPU pipeline, exported to {output_file}")
     return output_file
 
 
+def _fill_result(result, report, rate):
+    """_master_device's `result`: the loudness decision of the one track (report:
+    fetch_report's, empty when the stage did not run or failed) and the delivered rate"""
+    if result is not None:
+        modes, stats = report.get("modes"), report.get("stats")
+        result.update(mode=modes[0] if modes else "off", stats=stats[0] if stats else None,
+                      sample_rate=int(rate["sample_rate"]))
+
+
 def _master_multichannel(settings, status, progress, d_in, fs, frames, channels, s16, bounds, output_file,
-                         target=None):
+                         target=None, write=None, result=None):
     """master_audio for a file with 3..8 channels: the chain over the interleaved stream
     (:252), the measurement over the C channels and the C-channel alimiter
     (amx.engine.MultiChannelJob), with the same status strings and progress sequence.
@@ -239,9 +270,10 @@ def _master_multichannel(settings, status, progress, d_in, fs, frames, channels,
     settings key multichannel_dynamic is True: then MultiChannelJob.dynamic runs it (the
     master is at 192 kHz), and -- as for stereo, :243-246 -- an error in the loudness stage
     is logged and the track finalised without the gain.  target: the delivery rate
-    (settings key output_rate), None: the master's own."""
+    (settings key output_rate), None: the master's own.  write, result: as in _master_device."""
     import torch
     from amx.engine import MultiChannelJob, deliver
+    write = write or _write_output
     num_chunks = len(bounds)
     total_steps = num_chunks + 4
     job = MultiChannelJob(fs, channels, settings, frames, input_s16=s16, chunks=[(0, s, n) for s, n in bounds])
@@ -255,12 +287,14 @@ def _master_multichannel(settings, status, progress, d_in, fs, frames, channels,
     progress(num_chunks + 1, total_steps)                                     # :206
     status("Concatenation complete.")                                         # :213
     dyn = None
+    report = {}
     if settings.get("lufs") is not None:                                      # :216
         status("Normalizing final loudness...")                               # :217
         progress(num_chunks + 2, total_steps)                                 # :218
         if multichannel_dynamic(settings):
             try:
                 dyn = _normalize_multichannel(job)
+                report = job.report
             except Exception as e:                                            # :243-246
                 logging.exception("Error during disk-based normalization.")
                 if isinstance(e, subprocess.CalledProcessError):
@@ -269,7 +303,7 @@ def _master_multichannel(settings, status, progress, d_in, fs, frames, channels,
                 job.measure(lufs_on=False)
         else:
             job.measure(lufs_on=True)
-            rep = job.fetch_report(raise_dynamic=True)
+            rep = report = job.fetch_report(raise_dynamic=True)
             if rep["modes"] and rep["modes"][0] == "skip":
                 logging.warning("Measured loudness is -inf (silent audio). Skipping normalization.")
     else:
@@ -284,7 +318,8 @@ def _master_multichannel(settings, status, progress, d_in, fs, frames, channels,
         rate = {"sample_rate": dyn[1]["sample_rate"]}
         y = dyn[0]
     y = deliver(y, rate, target)
-    _write_output(output_file, y, rate["sample_rate"], settings)
+    _fill_result(result, report, rate)
+    write(output_file, y, rate["sample_rate"], settings)
     progress(total_steps, total_steps)                                        # :224
     logging.info(f"Finished GPU pipeline, exported to {output_file}")
     job.close()
@@ -335,3 +370,30 @@ def process_audio(settings, status_callback, progress_callback, art_callback, ta
 def master_array(x, sample_rate, settings, **kw):
     from amx.engine import master_array as _m
     return _m(x, sample_rate, settings, **kw)
+
+
+def master_files(jobs, status_callback=None, progress_callback=None, *, workers=None, staging_bytes=None,
+                 max_group_frames=None):
+    """master_audio for a list of settings dicts, with the host I/O overlapped and the
+    files that can share a plan batched (amx/files.py).  Every output file
+    is byte for byte the file master_audio(job) writes.
+
+    status_callback(index, message) and progress_callback(index, current, total): per job
+    index master_audio's own sequence; the sequences of different files may interleave, and
+    both are only ever called from the calling thread.
+
+    Returns one dict per job, in job order: index, input_file, output_file, error (None, or
+    the exception master_audio would have raised for that dict -- the other jobs still
+    finish, and a failed job leaves no output file), sample_rate (as delivered), mode
+    ("linear", "dynamic", "skip", "off"), stats (the pass-1 strings or None) and group (an
+    int: jobs that ran in one batched plan share it).  Only a `jobs` that is not a list of
+    dicts (TypeError), two jobs naming one output_file (ValueError) and a bad keyword
+    argument raise from the call itself, before any file is read.
+
+    workers: the I/O threads (default min(8, jobs), at most 16); staging_bytes: the bound on
+    pinned staging memory, half for reading ahead and half for writing behind (default
+    2 GiB; a larger file is staged alone); max_group_frames: the most frames in one plan
+    (default: what fits in half of the free device memory)."""
+    from amx import files
+    return files.master_files(sys.modules[__name__], jobs, status_callback, progress_callback, workers=workers,
+                              staging_bytes=staging_bytes, max_group_frames=max_group_frames)
